@@ -6,8 +6,14 @@ n.randomizations = 100, reference seeding n.cores = 1.  One step = one scde.expr
 call as the R shim makes it: the host count matrix is uploaded, then unique-count tables,
 per-cell NB/Poisson log-posterior tables, bootstrap joint posteriors for both groups, ratio
 posterior + lb/mle/ub/ce/Z summary, BH cZ, and the result table lands in host memory
-(SURVEY.md §8(d)'s wall time).  The same pass on counts already resident in HBM is reported
-beside it as device_resident_genes_per_s.
+(SURVEY.md §8(d)'s wall time).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value,
+ms_per_step, ...).  --full adds everything that takes passes of its own: the CPU baselines, the
+same pass on counts already resident in HBM (device_resident_genes_per_s), the per-stage
+HIP-event times, the FMA counter step and the roofline fields.  --dump-outputs DIR writes what
+the last timed step returned as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 --config 2: 20,000 genes x 200 cells (100/100), BASELINE configs[1].
 --config 4: scde.posteriors(return.individual.posterior.modes = TRUE) on 30,000 genes x 2,000
@@ -243,6 +249,41 @@ def cpu_baseline(cfg, models, counts, groups, prior, sample_genes):
     return sample_genes / dt, dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files of one run together
+DUMP_SAMPLE_SEED = 20240  # row samples of outputs over the limit: PCG64 of this, the same in every run
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per
+    array (float64; <name>.rank<r>.npy per rank in a multi-rank run).  Arrays are written whole
+    while the run's total stays within DUMP_LIMIT_BYTES; otherwise every array with more rows
+    than the sample takes the same fixed seeded sample of rows (ascending), whose indices go to
+    <name>_rows.npy."""
+    arrays = {k: np.atleast_1d(np.asarray(v)) for k, v in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    if sum(8 * a.size for a in arrays.values()) <= DUMP_LIMIT_BYTES:
+        out = dict(arrays)
+    else:
+        # rows kept per array: half the limit over the bytes of one row of every array (+ its index)
+        row_bytes = sum(8 * (a.size // max(a.shape[0], 1)) + 8 for a in arrays.values())
+        keep = max(1, (DUMP_LIMIT_BYTES // 2) // row_bytes)
+        for k, a in arrays.items():
+            if a.shape[0] <= keep:
+                out[k] = a
+                continue
+            rng = np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED))
+            rows = np.sort(rng.choice(a.shape[0], size=keep, replace=False))
+            out[k] = a[rows]
+            out[k + "_rows"] = rows
+    out = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in out.items()}
+    if sum(a.nbytes for a in out.values()) > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: the sampled outputs exceed the size limit")
+    suffix = f".rank{rank}" if world > 1 else ""
+    for k, a in out.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), a)
+
+
 def bench_prior(args, cfg, rank, world, device):
     """--config prior: scde.expression.prior on resident counts.  Roofline of the element
     pass that bins (k_prior_bin): it must read each count once (4 B per gene x cell)."""
@@ -254,7 +295,8 @@ def bench_prior(args, cfg, rank, world, device):
     dc = api.DeviceCounts(ctx, counts)
     for _ in range(args.warmup):
         prior = expression_prior(models, dc, length_out=LENGTH_OUT, ctx=ctx)
-    ctx.set_profiling(True)
+    if args.full:  # per-kernel HIP-event times of the timed steps
+        ctx.set_profiling(True)
     ctx.reset_kernel_times()
     ctx.synchronize()
     t0 = time.perf_counter()
@@ -262,6 +304,18 @@ def bench_prior(args, cfg, rank, world, device):
         prior = expression_prior(models, dc, length_out=LENGTH_OUT, ctx=ctx)
     ctx.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k.replace(".", "_"): prior[k] for k in ("x", "y", "lp", "grid.weight")},
+                     rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({"metric": METRIC_PRIOR, "value": NG * args.steps / dt, "unit": "genes/s",
+                              "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                              "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+                              "vs_baseline": None, "dtype": "f64"}))
+        dc.free()
+        ctx.close()
+        return
     kt = ctx.kernel_times()
     bin_ms, bin_n = kt["prior_bin"]
     bin_s = bin_ms / max(bin_n, 1) / 1e3
@@ -332,7 +386,8 @@ def bench_wpca(args, cfg, rank, world, device):
     kw = dict(n_components=2, n_randomizations=10, n_starts=10, seed=1, device=pdev)
     for _ in range(args.warmup):
         PG.pagoda_pathway_wPCA(None, sets, **kw)
-    ctx.set_profiling(True)
+    if args.full:  # per-kernel HIP-event times of the timed steps
+        ctx.set_profiling(True)
     ctx.reset_kernel_times()
     ctx.synchronize()
     t0 = time.perf_counter()
@@ -340,8 +395,25 @@ def bench_wpca(args, cfg, rank, world, device):
         out = PG.pagoda_pathway_wPCA(None, sets, **kw)
     ctx.synchronize()
     dt = time.perf_counter() - t0
-    kt = ctx.kernel_times()
     nsets = len(out)
+    if args.dump_outputs:
+        # every gene set's result in name order: sd and n per set, the 10 random sets' z, and xv
+        # (n.components rows of cells per set, stacked)
+        done = [out[k] for k in sorted(out) if out[k] is not None]
+        dump_outputs(args.dump_outputs, {"sd": np.vstack([r["sd"] for r in done]),
+                                         "z": np.vstack([r["z"].T for r in done]),
+                                         "n": np.array([[r["n"]] for r in done]),
+                                         "xv": np.vstack([r["xv"] for r in done])}, rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({"metric": METRIC_WPCA, "value": nsets * args.steps / dt, "unit": "gene sets/s",
+                              "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                              "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+                              "vs_baseline": None, "dtype": "f64"}))
+        pdev.free()
+        ctx.close()
+        return
+    kt = ctx.kernel_times()
     em_ms, em_n = kt["wpca_em"]
     # algorithmic work of one step's EM launches: replay the step's problems with iteration counts
     ctx.set_profiling(False)
@@ -447,7 +519,15 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
                     help="multi-GPU: strong = one fixed gene set split over the ranks (configs 3/4 default), "
                          "weak = a full gene set per rank")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="genes timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: CPU baselines, the device-resident rate, per-stage HIP-event "
+                         "times, the FMA counter step and the roofline fields (a plain run sets up, warms up, times "
+                         "--steps steps and prints metric / value / ms_per_step)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all: a fixed seeded row sample of larger outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="--full: genes timed on the CPU baseline (0 = skip)")
     ap.add_argument("--no-profile", action="store_true",
                     help="no HIP-event stage times and no counter step (rocprofv3 runs: tools/profile.sh)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -462,6 +542,8 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="context option for a study run (scde_ctx_set_option); the defaults are the product")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = dict(CONFIGS[args.config])
     cpu_sample = cfg["cpu_sample"] if args.cpu_sample is None else args.cpu_sample
 
@@ -623,10 +705,10 @@ def main():
     # so the GPU passes come last in the run and a coarse external GPU-busy sampler sees them
     cpu_fields = {}
     par = None
-    if rank == 0 and world == 1 and cpu_sample > 0 and args.cpu_workers > 0:
+    if args.full and rank == 0 and world == 1 and cpu_sample > 0 and args.cpu_workers > 0:
         par = cpu_baseline_parallel(cfg, models, counts, groups, prior, cpu_sample * args.cpu_workers,
                                     args.cpu_workers)
-    if rank == 0 and world == 1 and cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and cpu_sample > 0:
         what = ("batch + group posteriors, 3 ratio posteriors + summaries + BH" if batched else
                 "both groups + ratio + summary + BH" if de else "posteriors + modes")
         gps, secs = cpu_baseline(cfg, models, counts, groups, prior, cpu_sample)
@@ -668,6 +750,45 @@ def main():
                   # 16-bit uploads: the issuing thread's ms per step waiting for the narrowing
                   # threads, issuing copies + widening kernels, waiting for ring slots to free
                   "u16_ms_per_step": {k: ctx.stat(f"u16_{k}_ms") / args.steps for k in ("wait", "issue", "free")}}
+    if args.dump_outputs:
+        # the host arrays the last timed step filled, before any later pass writes them again
+        if de:
+            dump_outputs(args.dump_outputs, {"results": res}, rank, world)
+        else:
+            dump_outputs(args.dump_outputs, {"jp": jp, "modes": modes}, rank, world)
+    head = {
+        "metric": (METRIC_BATCH if batched else METRIC) if de else "genes/sec for scde.posteriors with posterior modes "
+                                                                   "(400-pt grid, 100 randomizations)",
+        "value": NTOT * args.steps / dt,
+        "unit": "genes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": f"synthetic (PCG64 seed {cfg['seed']}{'+rank' if scaling == 'weak' else ''}; o.ifm-resampled models; "
+                f"zero fraction {zero_frac:.3f})",
+        "config": {"workload": cfg["workload"], "genes_total": NTOT, "genes_per_gpu": NG, "cells": NC, "grid": G,
+                   "n_randomizations": NBOOT, "parallelism": f"gene-shard x{world} ({scaling})",
+                   "timed_region": "host counts -> upload -> unique tables, posteriors, ratio, summary, BH -> "
+                                   "host result table"},
+        **({"shard_of": args.shard_of,
+            "shard_note": "one process timing rank 0's shard of a strong split; value = all genes / that time "
+                          "(a projection, no collective, not the metric)"} if args.shard_of > 1 else {}),
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure alone (everything below takes passes of its own)
+        if args.trace_host:
+            timed()
+        if rank == 0:
+            print(json.dumps({**head, "host_syncs": sync_stats}))
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # device-resident rate (counts already in HBM), product settings
     dc = api.DeviceCounts(ctx, counts)
     dt_dev = timed(dc.ptr)
@@ -703,8 +824,6 @@ def main():
 
     if args.trace_host:
         timed()
-    total_genes = NTOT * args.steps
-    value = total_genes / dt
     boot_ms, boot_n = kt["boot"]
     boot_avg_s = (boot_ms / max(boot_n, 1)) / 1e3
     boot_step_s = boot_ms / 1e3 / args.steps
@@ -756,27 +875,7 @@ def main():
                          "perform it (sparse deltas over a shared baseline, post-checked tile skipping), so it "
                          "bounds nothing and is not a roofline fraction"}
     out = {
-        "metric": (METRIC_BATCH if batched else METRIC) if de else "genes/sec for scde.posteriors with posterior modes "
-                                                                   "(400-pt grid, 100 randomizations)",
-        "value": value,
-        "unit": "genes/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": f"synthetic (PCG64 seed {cfg['seed']}{'+rank' if scaling == 'weak' else ''}; o.ifm-resampled models; "
-                f"zero fraction {zero_frac:.3f})",
-        "config": {"workload": cfg["workload"], "genes_total": NTOT, "genes_per_gpu": NG, "cells": NC, "grid": G,
-                   "n_randomizations": NBOOT, "parallelism": f"gene-shard x{world} ({scaling})",
-                   "timed_region": "host counts -> upload -> unique tables, posteriors, ratio, summary, BH -> "
-                                   "host result table"},
-        **({"shard_of": args.shard_of,
-            "shard_note": "one process timing rank 0's shard of a strong split; value = all genes / that time "
-                          "(a projection, no collective, not the metric)"} if args.shard_of > 1 else {}),
+        **head,
         "device_resident_genes_per_s": NTOT * args.steps / dt_dev,
         "device_resident_ms_per_step": dt_dev / args.steps * 1e3,
         "roofline": roof,

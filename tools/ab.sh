@@ -11,7 +11,7 @@ for r in $(seq 1 ${AB_REPS:-2}); do
     IFS=: read -r name lib opts <<< "$spec"
     oargs=""
     for o in ${opts//,/ }; do oargs="$oargs --opt $o"; done
-    SCDE_LIB=$lib timeout -k 10 300 python bench.py ${AB_ARGS:---config 3} $oargs --steps ${AB_STEPS:-20} --warmup 3 \
+    SCDE_LIB=$lib timeout -k 10 300 python bench.py --full ${AB_ARGS:---config 3} $oargs --steps ${AB_STEPS:-20} --warmup 3 \
       --cpu-sample 0 --cpu-workers 0 > $out/${name}_$r.json 2> $out/${name}_$r.err || { tail -5 $out/${name}_$r.err; exit 1; }
     python - $out/${name}_$r.json $name <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ mkdir -p $out
 for spec in $KT_LIBS; do
   name=${spec%%:*}; lib=${spec#*:}
   SCDE_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name -o run -- \
-    python3 bench.py ${KT_ARGS:---config 3 --opt lanes=1} --steps 5 --warmup 2 --cpu-sample 0 --cpu-workers 0 --no-profile \
+    python3 bench.py --full ${KT_ARGS:---config 3 --opt lanes=1} --steps 5 --warmup 2 --cpu-sample 0 --cpu-workers 0 --no-profile \
     > $out/$name.log 2>&1 || { tail -5 $out/$name.log; exit 1; }
   f=$(find $out/$name -name "run_kernel_stats.csv" | head -1)
   python3 - "$f" "$name" "$re" <<'PY'

@@ -12,7 +12,7 @@ for spec in $PMC_LIBS; do
   oargs=""
   for o in ${opts//,/ }; do oargs="$oargs --opt $o"; done
   SCDE_LIB=$lib timeout -s KILL 150 rocprofv3 --pmc $PMC --output-format csv -d $out/$name -o run -- \
-    python3 bench.py ${PMC_ARGS:---config 3 --opt lanes=1} $oargs --steps 3 --warmup 1 --cpu-sample 0 --cpu-workers 0 \
+    python3 bench.py --full ${PMC_ARGS:---config 3 --opt lanes=1} $oargs --steps 3 --warmup 1 --cpu-sample 0 --cpu-workers 0 \
     --no-profile > $out/$name.log 2>&1 || { tail -5 $out/$name.log; exit 1; }
   f=$(find $out/$name -name "run_counter_collection.csv" | head -1)
   python3 - "$f" "$name" "$re" <<'PY'

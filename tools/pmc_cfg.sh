@@ -3,7 +3,7 @@
 out=$1; ctr=$2; shift 2
 export TMPDIR=/tmp
 mkdir -p $out
-timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d $out/pmc -o run -- python3 bench.py "$@" > $out/pmc.log 2>&1 || exit 1
+timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d $out/pmc -o run -- python3 bench.py --full "$@" > $out/pmc.log 2>&1 || exit 1
 python3 - $out <<'PY'
 import csv, glob, sys, collections
 rows = []

@@ -6,7 +6,7 @@ mkdir -p $out
 timeout -k 10 300 python -u -m pytest tests/test_gpu_skip.py tests/test_gpu_configs.py tests/test_gpu_fullsize.py -x -q \
   --timeout 180 --timeout-method thread > $out/tests.log 2>&1; rc=$?; tail -3 $out/tests.log; [ $rc -eq 0 ] || exit $rc
 for c in ${@:-3}; do
-  timeout -k 10 200 python bench.py --config $c --steps 10 --warmup 2 --cpu-sample 0 --cpu-workers 0 > $out/bc$c.log 2>&1 || exit 1
+  timeout -k 10 200 python bench.py --full --config $c --steps 10 --warmup 2 --cpu-sample 0 --cpu-workers 0 > $out/bc$c.log 2>&1 || exit 1
   python - "$out/bc$c.log" <<'PY'
 import json, sys
 for ln in open(sys.argv[1]):
