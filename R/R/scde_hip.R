@@ -188,3 +188,51 @@ scde.hip.varnorm.weights <- function(models, counts, prior, batch = NULL, n.rand
     if (!is.null(x$bmatw)) dimnames(x$bmatw) <- list(rownames(counts), rownames(models))
     list(avmodes = avmodes, modes = modes, matw = x$matw, bmatw = x$bmatw)
 }
+
+# ---- drop-out-adjusted cell-to-cell distances (vignettes/diffexp.md:231-301), each as.dist(1 - corr)
+# with boot::corr's weighted correlation computed on the GPU over all cell pairs.
+.scde.dist.counts <- function(models, counts) {
+    if (!all(rownames(models) %in% colnames(counts))) {
+        stop("ERROR: provided count data does not cover all of the cells specified in the model matrix")
+    }
+    counts <- as.matrix(counts[, match(rownames(models), colnames(counts)), drop = FALSE])
+    storage.mode(counts) <- "integer"
+    counts
+}
+
+.scde.as.dist <- function(x, models) {
+    dimnames(x) <- list(rownames(models), rownames(models))
+    as.dist(1 - x, upper = FALSE)
+}
+
+# reciprocal weighting (vignette 268-278)
+scde.reciprocal.dist <- function(models, counts, k = 0.95) {
+    counts <- .scde.dist.counts(models, counts)
+    m <- .scde.model.matrix(models)
+    .scde.as.dist(.Call("scde_hip_reciprocal_corr", m$mm, counts, m$squarelogit, k, PACKAGE = "scde"), models)
+}
+
+# mode-relative weighting (vignette 285-300); jp: scde.posteriors(..., return.individual.posterior.modes = TRUE),
+# computed here when absent.  max.col's random tie-break is replaced by the first maximum.
+scde.mode.fail.dist <- function(models, counts, prior, jp = NULL, n.randomizations = 100, n.cores = 1) {
+    if (is.null(jp)) {
+        jp <- scde.posteriors(models, counts, prior, n.randomizations = n.randomizations, n.cores = n.cores,
+                              return.individual.posterior.modes = TRUE)
+    }
+    counts <- .scde.dist.counts(models, counts)
+    m <- .scde.model.matrix(models)
+    jp.modes <- log(10^prior$x - 1)[max.col(jp$jp, ties.method = "first")]
+    .scde.as.dist(.Call("scde_hip_mode_fail_corr", m$mm, counts, m$squarelogit, jp$modes, jp.modes,
+                        PACKAGE = "scde"), models)
+}
+
+# direct drop-out (vignette 241-258).  The draws come from the library's counter-based generator
+# keyed by seed (by default drawn from R's RNG, so set.seed() governs the result), or from
+# uniforms: n.simulations x cells x genes values of runif().
+scde.direct.dist <- function(models, counts, n.simulations = 10, k = 0.9, seed = NULL, uniforms = NULL) {
+    counts <- .scde.dist.counts(models, counts)
+    m <- .scde.model.matrix(models)
+    if (is.null(seed)) seed <- floor(runif(1) * 2^53)
+    .scde.as.dist(.Call("scde_hip_direct_corr", m$mm, counts, m$squarelogit, k, n.simulations, uniforms, seed,
+                        PACKAGE = "scde"), models)
+}

@@ -13,7 +13,7 @@
  *   winsorizeMatrix, matWCorr, plSemicompleteCor2, matCorr  src/pagoda.cpp (decl src/pagoda.h:5-8)
  * Layer 2 (the fused device path behind R/scde_hip.R's wrappers):
  *   scde_hip_expression_difference, scde_hip_expression_difference_batch, scde_hip_posteriors,
- *   scde_hip_varnorm_weights
+ *   scde_hip_varnorm_weights, scde_hip_reciprocal_corr, scde_hip_mode_fail_corr, scde_hip_direct_corr
  *
  * Build: src/Makevars adds -I$(SCDE_HIP_HOME)/include and -lscde_hip.
  * Errors from the library become Rf_error; there is no CPU fallback.
@@ -419,5 +419,58 @@ SEXP scde_hip_varnorm_weights(SEXP Models, SEXP Counts, SEXP PriorX, SEXP Nboot,
   SEXP out = PROTECT(Rf_mkNamed(VECSXP, nm));
   SET_VECTOR_ELT(out, 0, modes); SET_VECTOR_ELT(out, 1, matw); SET_VECTOR_ELT(out, 2, bmatw);
   UNPROTECT(7);
+  return out;
+}
+
+/* ---- cell-to-cell distance measures (vignettes/diffexp.md:231-301; R/R/scde_hip.R's
+ * scde.reciprocal.dist / scde.mode.fail.dist / scde.direct.dist).  Each returns the ncells x
+ * ncells correlation matrix; the wrappers return as.dist(1 - .). */
+SEXP scde_hip_reciprocal_corr(SEXP Models, SEXP Counts, SEXP SquareLogitConc, SEXP K) {
+  SEXP mm = PROTECT(Rf_coerceVector(Models, REALSXP)), ci = PROTECT(Rf_coerceVector(Counts, INTSXP));
+  const int ngenes = Rf_nrows(Counts), ncells = Rf_ncols(Counts);
+  if (Rf_nrows(Models) != ncells) Rf_error("scde_hip_reciprocal_corr: models and counts disagree on the cells");
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, ncells, ncells));
+  chk(scde_reciprocal_corr_host(NULL, INTEGER(ci), ngenes, ngenes, ncells, REAL(mm), as_int(SquareLogitConc),
+                                Rf_asReal(K), REAL(out)));
+  UNPROTECT(3);
+  return out;
+}
+
+SEXP scde_hip_mode_fail_corr(SEXP Models, SEXP Counts, SEXP SquareLogitConc, SEXP Modes, SEXP JpModes) {
+  SEXP mm = PROTECT(Rf_coerceVector(Models, REALSXP)), ci = PROTECT(Rf_coerceVector(Counts, INTSXP));
+  SEXP mo = PROTECT(Rf_coerceVector(Modes, REALSXP)), jm = PROTECT(Rf_coerceVector(JpModes, REALSXP));
+  const int ngenes = Rf_nrows(Counts), ncells = Rf_ncols(Counts);
+  if (Rf_nrows(Models) != ncells) Rf_error("scde_hip_mode_fail_corr: models and counts disagree on the cells");
+  if (Rf_nrows(Modes) != ngenes || Rf_ncols(Modes) != ncells || XLENGTH(jm) != ngenes)
+    Rf_error("scde_hip_mode_fail_corr: modes must be genes x cells and jp.modes one value per gene");
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, ncells, ncells));
+  chk(scde_mode_fail_corr_host(NULL, INTEGER(ci), ngenes, ngenes, ncells, REAL(mm), as_int(SquareLogitConc), REAL(mo),
+                               REAL(jm), REAL(out)));
+  UNPROTECT(5);
+  return out;
+}
+
+/* Uniforms: NULL (the library's generator, keyed by Seed) or n.simulations x ncells x ngenes draws */
+SEXP scde_hip_direct_corr(SEXP Models, SEXP Counts, SEXP SquareLogitConc, SEXP K, SEXP NSim, SEXP Uniforms,
+                          SEXP Seed) {
+  SEXP mm = PROTECT(Rf_coerceVector(Models, REALSXP)), ci = PROTECT(Rf_coerceVector(Counts, INTSXP));
+  const int ngenes = Rf_nrows(Counts), ncells = Rf_ncols(Counts), nsim = as_int(NSim);
+  if (Rf_nrows(Models) != ncells) Rf_error("scde_hip_direct_corr: models and counts disagree on the cells");
+  const double *unif = NULL;
+  int np = 2;
+  if (Uniforms != R_NilValue) {
+    SEXP u = PROTECT(Rf_coerceVector(Uniforms, REALSXP));
+    np++;
+    if (nsim < 1 || (double) XLENGTH(u) != (double) nsim * ncells * ngenes)
+      Rf_error("scde_hip_direct_corr: uniforms must hold n.simulations x cells x genes values");
+    unif = REAL(u);
+  }
+  const double sd = Rf_asReal(Seed);
+  if (!(sd >= 0 && sd < 18446744073709551616.0)) Rf_error("scde_hip_direct_corr: seed must be in [0, 2^64)");
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, ncells, ncells));
+  np++;
+  chk(scde_direct_corr_host(NULL, INTEGER(ci), ngenes, ngenes, ncells, REAL(mm), as_int(SquareLogitConc),
+                            Rf_asReal(K), nsim, unif, (uint64_t) sd, REAL(out)));
+  UNPROTECT(np);
   return out;
 }

@@ -387,6 +387,56 @@ int scde_matCorr(const double* x, int nrow, int nx, const double* y, int ny, dou
  * the shared genes (np x np, 1 on the diagonal), n = union sizes (np x np, 0 on it). */
 int scde_plSemicompleteCor2(int np, const int64_t* off, const int* idx, const double* val, double* r, int* n);
 
+/* ---------------------------------------------------------------- cell-to-cell distance measures
+ * The vignette's "Adjusted distance measures" (vignettes/diffexp.md:231-301).  Each entry writes
+ * the weighted correlation of every pair of cells, out: ncells x ncells col-major, host, both
+ * triangles filled (the distance is 1 - out):
+ *   corr(x, y, w) = (Sxy/s - m1 m2) / sqrt((Sxx/s - m1^2) (Syy/s - m2^2)),  s = sum w,
+ *   m1 = sum(x w)/s, m2 = sum(y w)/s, Sxy = sum(x y w), Sxx = sum(x^2 w), Syy =
+ *   sum(y^2 w) (boot::corr); a pair with zero weight sum or zero weighted variance is NaN.
+ * _dev entries take device-resident data (int32 counts, leading dimension ld), _host entries
+ * host data they stage themselves; ctx may be NULL (the default context).  models: ncells x 12
+ * col-major as everywhere.  SCDE_EARG: null pointers, ncells < 1, k outside [0, 1], nsim < 1. */
+
+/* Weights that factor per cell, w_g(i, j) = u[g, i] u[g, j]; x, u: ngenes x ncells col-major. */
+int scde_wcorr_sep_dev(scde_ctx* ctx, const double* x_dev, const double* u_dev, int64_t ld, int ngenes, int ncells,
+                       double* out);
+int scde_wcorr_sep_host(scde_ctx* ctx, const double* x, const double* u, int64_t ld, int ngenes, int ncells,
+                        double* out);
+
+/* Reciprocal weighting (vignette 268-278): x = log10(counts + 1),
+ * w = sqrt((1 - f(model_i, fpm[g, j])) (1 - f(model_j, fpm[g, i]))) k + (1 - k), f =
+ * scde.failure.probability, fpm = scde.expression.magnitude. */
+int scde_reciprocal_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const double* models, int square_logit_conc, double k, double* out);
+int scde_reciprocal_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const double* models, int square_logit_conc, double k, double* out);
+
+/* Mode-relative weighting (vignette 285-300).  modes: ngenes x ncells posterior modes
+ * (natural-log magnitudes, host; -inf allowed); jp_modes: per gene, the joint posterior's mode
+ * as log(10^prior_x - 1) (host).  x = log10(exp(modes) + 1),
+ * w = (matw_i matw_j)^(1/4), matw = 1 - sqrt(p.self.fail sqrt(p.self.fail p.mode.fail)). */
+int scde_mode_fail_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                            const double* models, int square_logit_conc, const double* modes,
+                            const double* jp_modes, double* out);
+int scde_mode_fail_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                             const double* models, int square_logit_conc, const double* modes,
+                             const double* jp_modes, double* out);
+
+/* Direct drop-out (vignette 241-258): the mean over nsim rounds of the pairwise-complete
+ * Pearson correlation of log10(counts + 1) with entry (g, c) kept with probability
+ * q = 1 - p.self.fail[g, c] k.  From a uniform u01: q == 0 drops, q == 1 keeps, q <= 0.5 keeps
+ * iff u01 >= 1 - q, q > 0.5 keeps iff u01 < q.  uniforms: host, nsim x ncells x ngenes (round
+ * s, cell c, gene g at (s ncells + c) ngenes + g), or NULL for the library's counter-based
+ * generator: key_s = mix64(seed + 0x9E3779B97F4A7C15 (s + 1)),
+ * u01 = (mix64(key_s ^ mix64(g + ngenes c + 1)) >> 11) 2^-53, mix64 the splitmix64 finalizer. */
+int scde_direct_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                         const double* models, int square_logit_conc, double k, int nsim, const double* uniforms,
+                         uint64_t seed, double* out);
+int scde_direct_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* models,
+                          int square_logit_conc, double k, int nsim, const double* uniforms, uint64_t seed,
+                          double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ EXPORTS = [
     "scde_pagoda_varnorm_weights_dev", "scde_pagoda_varnorm_weights_host",
     "scde_baileyWPCA", "scde_bwpca_batch_dev", "scde_r_set_seed", "scde_r_unif_rand", "scde_r_sample",
     "scde_shuffle_perms", "scde_winsorizeMatrix", "scde_matWCorr", "scde_matCorr", "scde_plSemicompleteCor2",
+    "scde_wcorr_sep_dev", "scde_wcorr_sep_host", "scde_reciprocal_corr_dev", "scde_reciprocal_corr_host",
+    "scde_mode_fail_corr_dev", "scde_mode_fail_corr_host", "scde_direct_corr_dev", "scde_direct_corr_host",
 ]
 
 
@@ -124,6 +126,11 @@ def lib():
     L.scde_matWCorr.argtypes = [P, P, i, i, P]
     L.scde_matCorr.argtypes = [P, i, i, P, i, P]
     L.scde_plSemicompleteCor2.argtypes = [i, P, P, P, P, P]
+    L.scde_wcorr_sep_dev.argtypes = L.scde_wcorr_sep_host.argtypes = [P, P, P, i64, i, i, P]
+    L.scde_reciprocal_corr_dev.argtypes = L.scde_reciprocal_corr_host.argtypes = [P, P, i64, i, i, P, i, d, P]
+    L.scde_mode_fail_corr_dev.argtypes = L.scde_mode_fail_corr_host.argtypes = [P, P, i64, i, i, P, i, P, P, P]
+    L.scde_direct_corr_dev.argtypes = L.scde_direct_corr_host.argtypes = [P, P, i64, i, i, P, i, d, i, P,
+                                                                         ctypes.c_uint64, P]
     _lib = L
     return L
 

@@ -258,6 +258,9 @@ struct scde_ctx {
   Buf wp_probs, wp_blocks, wp_kidx, wp_cols, wp_perms, wp_starts, wp_scratch, wp_stat, wp_out, wp_smooth, wp_M, wp_W;
   // PAGODA helpers
   Buf pg_a, pg_b, pg_c, pg_d, pg_e;
+  // cell-to-cell distance measures (dist.hip): X, U, fpm / modes, p.self.fail / uniforms, per-cell
+  // constants, per-gene modes, the C x C result
+  Buf ds_x, ds_u, ds_f, ds_p, ds_x0, ds_cell, ds_jpm, ds_out;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters
@@ -574,6 +577,7 @@ struct scde_ctx {
                  &wp_stat,  &wp_out,     &wp_smooth, &wp_M,    &wp_W,     &pr_cell,   &pr_part,
                  &pr_occ,   &pr_stats,   &pr_hist, &pr_work,   &pr_out,   &pr_v,      &pr_sorted, &pr_sortw,
                  &pg_a,     &pg_b,       &pg_c,    &pg_d,      &pg_e,      &counts_in, &w8,
+                 &ds_x,     &ds_u,       &ds_f,    &ds_p,      &ds_x0,     &ds_cell,   &ds_jpm,   &ds_out,
                  &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &ellw,  &excd, &gdone};
     for (Buf* b : wp) b->release();
     for (auto& u : us) u.release();
@@ -4279,6 +4283,189 @@ int scde_plSemicompleteCor2(int np, const int64_t* off, const int* idx, const do
   HCHK(hipMemcpyAsync(r, cx->pg_d.p, sizeof(double) * nn, hipMemcpyDeviceToHost, cx->stream));
   HCHK(hipMemcpyAsync(n, cx->pg_e.p, sizeof(int) * nn, hipMemcpyDeviceToHost, cx->stream));
   return cx->sync();
+}
+
+// ------------------------------------------------------------------ cell-to-cell distance measures
+// The vignette's "Adjusted distance measures" (vignettes/diffexp.md:231-301) on the device
+// (dist.hip).  Arguments are checked before the GPU is touched.
+static int dist_check(const void* in, int64_t ld, int ngenes, int ncells, const double* models, const double* out) {
+  if (!in || !models || !out) return fail(SCDE_EARG, "null argument");
+  if (ncells < 1) return fail(SCDE_EARG, "ncells must be at least 1");
+  if (ngenes < 0 || ld < ngenes) return fail(SCDE_EARG, "bad dimensions");
+  return SCDE_OK;
+}
+
+// per-cell constants corr.b, corr.a, conc.b, conc.a, conc.a2 (model columns 3, 4, 0, 1, 11)
+static int dist_cellp(scde_ctx* ctx, const double* models, int C, int sq) {
+  std::vector<double> cellp((size_t)5 * C);
+  const int mcol[5] = {3, 4, 0, 1, 11};
+  for (int j = 0; j < 5; ++j)
+    for (int c = 0; c < C; ++c) cellp[(size_t)j * C + c] = (j == 4 && !sq) ? 0.0 : models[(size_t)mcol[j] * C + c];
+  return upload(ctx, ctx->ds_cell, cellp.data(), sizeof(double) * cellp.size());
+}
+
+static int dist_out(scde_ctx* ctx, int C, double* out) {
+  HCHK(hipMemcpyAsync(out, ctx->ds_out.p, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
+}
+
+// a host N x C column-major matrix (leading dimension ld) into a dense device buffer
+static int dist_put(scde_ctx* ctx, Buf& b, const double* src, int64_t ld, int N, int C) {
+  const size_t row = sizeof(double) * (size_t)N;
+  HCHK(b.ensure(std::max<size_t>(1, row * C)));
+  if (N == 0) return SCDE_OK;
+  if (ld == N) HCHK(hipMemcpyAsync(b.p, src, row * C, hipMemcpyHostToDevice, ctx->stream));
+  else
+    HCHK(hipMemcpy2DAsync(b.p, row, src, sizeof(double) * (size_t)ld, row, C, hipMemcpyHostToDevice, ctx->stream));
+  return SCDE_OK;
+}
+
+int scde_wcorr_sep_dev(scde_ctx* ctx, const double* x_dev, const double* u_dev, int64_t ld, int ngenes, int ncells,
+                       double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(x_dev, ld, ngenes, ncells, u_dev, out));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)ncells * ncells));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);  // the pair kernels are timed in slot "other"
+  HCHK(launch_wcorr_gram(x_dev, u_dev, ld, ngenes, ncells, ctx->ds_out.as<double>(), 0, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return dist_out(ctx, ncells, out);
+}
+
+int scde_wcorr_sep_host(scde_ctx* ctx, const double* x, const double* u, int64_t ld, int ngenes, int ncells,
+                        double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(x, ld, ngenes, ncells, u, out));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  RCHK(dist_put(ctx, ctx->ds_x, x, ld, ngenes, ncells));
+  RCHK(dist_put(ctx, ctx->ds_u, u, ld, ngenes, ncells));
+  return scde_wcorr_sep_dev(ctx, ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ngenes, ngenes, ncells, out);
+}
+
+int scde_reciprocal_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const double* models, int square_logit_conc, double k, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts_dev, ld, ngenes, ncells, models, out));
+  if (!(k >= 0 && k <= 1)) return fail(SCDE_EARG, "k must be in [0, 1]");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  const int N = ngenes, C = ncells, sq = square_logit_conc != 0;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)N * C);
+  RCHK(dist_cellp(ctx, models, C, sq));
+  HCHK(ctx->ds_x.ensure(nb));
+  HCHK(ctx->ds_f.ensure(nb));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)C * C));
+  HCHK(launch_dist_prep(counts_dev, ld, N, C, ctx->ds_cell.as<double>(), sq, ctx->ds_x.as<double>(),
+                        ctx->ds_f.as<double>(), nullptr, ctx->stream));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_recip_corr(ctx->ds_x.as<double>(), ctx->ds_f.as<double>(), N, C, ctx->ds_cell.as<double>(), sq, k,
+                         ctx->ds_out.as<double>(), ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return dist_out(ctx, C, out);
+}
+
+int scde_reciprocal_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const double* models, int square_logit_conc, double k, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts, ld, ngenes, ncells, models, out));
+  if (!(k >= 0 && k <= 1)) return fail(SCDE_EARG, "k must be in [0, 1]");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_reciprocal_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, k, out);
+}
+
+int scde_mode_fail_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                            const double* models, int square_logit_conc, const double* modes,
+                            const double* jp_modes, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts_dev, ld, ngenes, ncells, models, out));
+  if (!modes || !jp_modes) return fail(SCDE_EARG, "null argument");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  const int N = ngenes, C = ncells, sq = square_logit_conc != 0;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)N * C);
+  RCHK(dist_cellp(ctx, models, C, sq));
+  RCHK(dist_put(ctx, ctx->ds_f, modes, N, N, C));
+  RCHK(dist_put(ctx, ctx->ds_jpm, jp_modes, N, N, 1));
+  HCHK(ctx->ds_x.ensure(nb));
+  HCHK(ctx->ds_u.ensure(nb));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)C * C));
+  HCHK(launch_dist_mode_prep(counts_dev, ld, N, C, ctx->ds_cell.as<double>(), sq, ctx->ds_f.as<double>(),
+                             ctx->ds_jpm.as<double>(), ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ctx->stream));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_wcorr_gram(ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), N, N, C, ctx->ds_out.as<double>(), 0,
+                         ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return dist_out(ctx, C, out);
+}
+
+int scde_mode_fail_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                             const double* models, int square_logit_conc, const double* modes,
+                             const double* jp_modes, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts, ld, ngenes, ncells, models, out));
+  if (!modes || !jp_modes) return fail(SCDE_EARG, "null argument");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_mode_fail_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, modes, jp_modes, out);
+}
+
+static int direct_check(double k, int nsim) {
+  if (!(k >= 0 && k <= 1)) return fail(SCDE_EARG, "k must be in [0, 1]");
+  if (nsim < 1) return fail(SCDE_EARG, "nsim must be at least 1");
+  return SCDE_OK;
+}
+
+int scde_direct_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                         const double* models, int square_logit_conc, double k, int nsim, const double* uniforms,
+                         uint64_t seed, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts_dev, ld, ngenes, ncells, models, out));
+  RCHK(direct_check(k, nsim));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  const int N = ngenes, C = ncells, sq = square_logit_conc != 0;
+  const long long NC = (long long)N * C;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)NC);
+  RCHK(dist_cellp(ctx, models, C, sq));
+  HCHK(ctx->ds_x0.ensure(nb));
+  HCHK(ctx->ds_p.ensure(nb));
+  HCHK(ctx->ds_x.ensure(nb));
+  HCHK(ctx->ds_u.ensure(nb));
+  if (uniforms) HCHK(ctx->ds_f.ensure(nb));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)C * C));
+  HCHK(launch_dist_prep(counts_dev, ld, N, C, ctx->ds_cell.as<double>(), sq, ctx->ds_x0.as<double>(), nullptr,
+                        ctx->ds_p.as<double>(), ctx->stream));
+  // the rounds run one after the other on the stream and add into the result in round order
+  for (int s = 0; s < nsim; ++s) {
+    if (uniforms && NC)
+      HCHK(hipMemcpyAsync(ctx->ds_f.p, uniforms + (size_t)s * NC, sizeof(double) * NC, hipMemcpyHostToDevice,
+                          ctx->stream));
+    HCHK(launch_dist_direct_prep(ctx->ds_x0.as<double>(), ctx->ds_p.as<double>(), NC, k,
+                                 uniforms ? ctx->ds_f.as<double>() : nullptr, dist_sim_key(seed, s),
+                                 ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ctx->stream));
+    hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+    HCHK(launch_wcorr_gram(ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), N, N, C, ctx->ds_out.as<double>(), s > 0,
+                           ctx->stream));
+    ctx->mark_end(SLOT_OTHER, ev);
+  }
+  RCHK(dist_out(ctx, C, out));
+  for (size_t e = 0; e < (size_t)C * C; ++e) out[e] /= (double)nsim;
+  return SCDE_OK;
+}
+
+int scde_direct_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* models,
+                          int square_logit_conc, double k, int nsim, const double* uniforms, uint64_t seed,
+                          double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts, ld, ngenes, ncells, models, out));
+  RCHK(direct_check(k, nsim));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_direct_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, k, nsim, uniforms, seed,
+                              out);
 }
 }  // extern "C"
 

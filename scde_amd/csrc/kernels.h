@@ -30,6 +30,8 @@
 #endif
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 namespace scde {
 
 // k_col_consts record per column: [n or -1, n - x, stirlerr sum, 0.5 lf, log(size/(size+x)),
@@ -400,5 +402,26 @@ hipError_t launch_vn_modes(const double* jp, long long jg, long long jk, int nge
 hipError_t launch_vn_matw(const int* counts, long long ld, int ngenes, const int* cellidx, int ncells,
                           const double* models, int mld, int sq, const double* modes, const long long* mode_off,
                           double* matw, hipStream_t s);
+
+// ---- drop-out-adjusted cell-to-cell correlations (dist.hip; vignettes/diffexp.md:231-301).
+// Matrices genes x cells column-major; cellp: 5 x C (corr.b, corr.a, conc.b, conc.a, conc.a2).
+// x = log10(cd + 1), fpm = scde.expression.magnitude, pself = scde.failure.probability at fpm
+// (each nullable), from resident counts
+hipError_t launch_dist_prep(const int* counts, long long ld, int N, int C, const double* cellp, int sq, double* x,
+                            double* fpm, double* pself, hipStream_t s);
+// the mode-relative measure's X = log10(exp(modes) + 1) and U = matw^(1/4)
+hipError_t launch_dist_mode_prep(const int* counts, long long ld, int N, int C, const double* cellp, int sq,
+                                 const double* modes, const double* jpm, double* x, double* u, hipStream_t s);
+// one simulation of the direct measure: masked X / U from uniforms (unif, or the generator keyed
+// by dist_sim_key(seed, simulation) when unif is null)
+uint64_t dist_sim_key(uint64_t seed, int sim);
+hipError_t launch_dist_direct_prep(const double* xin, const double* pself, long long NC, double k,
+                                   const double* unif, uint64_t key, double* x, double* u, hipStream_t s);
+// correlation with weights u[g, i] u[g, j] (out C x C, both triangles; accumulate: out += corr)
+hipError_t launch_wcorr_gram(const double* X, const double* U, long long ld, int N, int C, double* out,
+                             int accumulate, hipStream_t s);
+// correlation with the reciprocal weights (X, F dense N x C)
+hipError_t launch_recip_corr(const double* X, const double* F, int N, int C, const double* cellp, int sq, double k,
+                             double* out, hipStream_t s);
 
 }  // namespace scde
