@@ -437,6 +437,66 @@ int scde_direct_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngen
                           int square_logit_conc, double k, int nsim, const double* uniforms, uint64_t seed,
                           double* out);
 
+/* ---------------------------------------------------------------- hierarchical clustering
+ * R's stats::hclust for the monotone linkages, and what cutree needs, on the device
+ * (csrc/hclust.hip: one workgroup per problem, the whole merge loop in one launch).
+ *
+ * Input.  n >= 2 objects; d: n x n doubles, column-major, leading dimension ld >= n.  Only the
+ * strict lower triangle is read (d(i, j) at d[i + j * ld], i > j) -- what as.dist reads; the
+ * diagonal and the upper triangle are never read (scde_matWCorr fills only the lower triangle).
+ * Every value read must be finite: otherwise SCDE_EARG, the message naming the first offending
+ * pair in column-major order (stats::hclust refuses NA/NaN/Inf).  n < 2 is SCDE_EARG.  The
+ * caller's matrix is never written.
+ *
+ * method: 0 ward.D, 1 ward.D2, 2 single, 3 complete, 4 average, 5 mcquitty; any other code is
+ * SCDE_EARG (centroid and median are not monotone and are not offered).
+ *
+ * One step.  Among the active clusters the pair to merge is the lexicographic minimum of
+ * (d(i, j), i, j), i < j; values are compared numerically (-0.0 ties with 0.0).  For these
+ * linkages that is the pair stats::hclust's nearest-neighbour list picks, ties included (read
+ * from its algorithm, not checked against a run of R).  The merged cluster keeps slot i, slot j
+ * dies, size[i] += size[j].  Every other active k is updated in float64, each expression
+ * evaluated left to right as written, no fused multiply-add (ni, nj, nk the sizes as doubles,
+ * h = d(i, j)):
+ *   ward.D, ward.D2   ((ni + nk) * dik + (nj + nk) * djk - nk * h) / (ni + nj + nk)
+ *   single            min(dik, djk)
+ *   complete          max(dik, djk)
+ *   average           (ni * dik + nj * djk) / (ni + nj)
+ *   mcquitty          (dik + djk) / 2
+ * ward.D2 squares every input value once on the way in (d * d) and reports sqrt(h), the square
+ * root taken in host code.
+ *
+ * Outputs (host), in R's encoding.
+ *   merge   (n - 1) x 2 ints, column-major.  Negative: a singleton, -(1-based index); positive:
+ *           the 1-based step that made the cluster.  Within a row a singleton comes before a
+ *           cluster, two singletons in increasing index, two clusters in increasing step.
+ *   height  n - 1 doubles.
+ *   order   n ints, 1-based: the leaves left to right from expanding the last step
+ *           recursively, column 1 as the left child.
+ * cutree: k clusters are the state after n - k steps; a height h gives
+ * k = n - #{height <= h} (non-monotone heights are an error); labels are 1-based, clusters
+ * numbered by the first observation they contain.
+ *
+ * SCDE_EHIP with an "out of memory" message, before any launch, when the workspace (n^2 + O(n)
+ * doubles per problem) cannot be allocated.  ctx may be NULL (the default context). */
+int scde_hclust_host(scde_ctx* ctx, const double* d, int64_t ld, int n, int method, int* merge, double* height,
+                     int* order);
+/* d_dev is resident in HBM and is left unmodified; results go to the host. */
+int scde_hclust_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, int method, int* merge, double* height,
+                    int* order);
+/* nprob problems packed in one device buffer: problem p is n[p] x n[p] at element off[p],
+ * ld = n[p].  One launch, one workgroup per problem.  Outputs packed in problem order: merge of
+ * problem p at 2 * sum_{q<p}(n[q] - 1), height at sum_{q<p}(n[q] - 1), order at sum_{q<p} n[q].
+ * A non-finite value in any problem is SCDE_EARG naming the (0-based) problem. */
+int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int* n,
+                          int method, int* merge, double* height, int* order);
+
+/* 1 - cor(x) of the columns of a resident nrow x ncol column-major matrix (the correlation of
+ * scde_matCorr), written to the resident ncol x ncol matrix out_dev, both triangles, the
+ * diagonal exactly 0 (as.matrix(as.dist(.))): pagoda.gene.clusters' gene-to-gene distance, ready
+ * for scde_hclust_dev. */
+int scde_cor_distance_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ EXPORTS = [
     "scde_shuffle_perms", "scde_winsorizeMatrix", "scde_matWCorr", "scde_matCorr", "scde_plSemicompleteCor2",
     "scde_wcorr_sep_dev", "scde_wcorr_sep_host", "scde_reciprocal_corr_dev", "scde_reciprocal_corr_host",
     "scde_mode_fail_corr_dev", "scde_mode_fail_corr_host", "scde_direct_corr_dev", "scde_direct_corr_host",
+    "scde_hclust_host", "scde_hclust_dev", "scde_hclust_batch_dev", "scde_cor_distance_dev",
 ]
 
 
@@ -131,6 +132,9 @@ def lib():
     L.scde_mode_fail_corr_dev.argtypes = L.scde_mode_fail_corr_host.argtypes = [P, P, i64, i, i, P, i, P, P, P]
     L.scde_direct_corr_dev.argtypes = L.scde_direct_corr_host.argtypes = [P, P, i64, i, i, P, i, d, i, P,
                                                                          ctypes.c_uint64, P]
+    L.scde_hclust_host.argtypes = L.scde_hclust_dev.argtypes = [P, P, i64, i, i, P, P, P]
+    L.scde_hclust_batch_dev.argtypes = [P, i, P, P, P, i, P, P, P]
+    L.scde_cor_distance_dev.argtypes = [P, P, i, i, P]
     _lib = L
     return L
 

@@ -261,6 +261,9 @@ struct scde_ctx {
   // cell-to-cell distance measures (dist.hip): X, U, fpm / modes, p.self.fail / uniforms, per-cell
   // constants, per-gene modes, the C x C result
   Buf ds_x, ds_u, ds_f, ds_p, ds_x0, ds_cell, ds_jpm, ds_out;
+  // hierarchical clustering (hclust.hip): a host matrix staged, the problems' workspaces, the
+  // problem descriptors, the raw steps (oi, oj, oh, flags)
+  Buf hc_in, hc_ws, hc_prob, hc_out;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters
@@ -578,6 +581,7 @@ struct scde_ctx {
                  &pr_occ,   &pr_stats,   &pr_hist, &pr_work,   &pr_out,   &pr_v,      &pr_sorted, &pr_sortw,
                  &pg_a,     &pg_b,       &pg_c,    &pg_d,      &pg_e,      &counts_in, &w8,
                  &ds_x,     &ds_u,       &ds_f,    &ds_p,      &ds_x0,     &ds_cell,   &ds_jpm,   &ds_out,
+                 &hc_in,    &hc_ws,      &hc_prob, &hc_out,
                  &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &ellw,  &excd, &gdone};
     for (Buf* b : wp) b->release();
     for (auto& u : us) u.release();
@@ -4466,6 +4470,128 @@ int scde_direct_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngen
   RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
   return scde_direct_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, k, nsim, uniforms, seed,
                               out);
+}
+
+// ------------------------------------------------------------------ hierarchical clustering
+// stats::hclust / cutree's tree for the monotone linkages (hclust.hip; contract in scde_hip.h).
+// Arguments are checked before the GPU is touched.
+static int hclust_run(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int64_t* ldv,
+                      const int* n, int method, int* merge, double* height, int* order) {
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  std::vector<HclustProblem> pr(nprob);
+  size_t wsb = 0, steps = 0;
+  for (int p = 0; p < nprob; ++p) {
+    pr[p] = {(long long)off[p], (long long)ldv[p], (long long)wsb, (long long)steps, n[p]};
+    wsb += hclust_ws_bytes(n[p]);
+    steps += (size_t)n[p] - 1;
+  }
+  // the workspace comes first: a problem that does not fit fails here, before any launch
+  if (ctx->hc_ws.ensure(wsb) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "hclust: out of memory: the workspace of %d problem(s) needs %zu bytes of device memory",
+                nprob, wsb);
+  }
+  RCHK(upload(ctx, ctx->hc_prob, pr.data(), sizeof(HclustProblem) * pr.size()));
+  // oh (doubles), flags (long long), oi, oj (ints)
+  const size_t ob = steps * (sizeof(double) + 2 * sizeof(int)) + sizeof(long long) * nprob;
+  HCHK(ctx->hc_out.ensure(ob));
+  double* oh = ctx->hc_out.as<double>();
+  long long* flag = reinterpret_cast<long long*>(oh + steps);
+  int* oi = reinterpret_cast<int*>(flag + nprob);
+  int* oj = oi + steps;
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_hclust(d_dev, ctx->hc_prob.as<HclustProblem>(), nprob, method, ctx->hc_ws.as<char>(), oi, oj, oh, flag,
+                     ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  std::vector<char> host(ob);
+  HCHK(hipMemcpyAsync(host.data(), ctx->hc_out.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  if (wsb > ((size_t)1 << 30)) ctx->hc_ws.release();  // a 20,000-object workspace is 3.2 GB: not kept
+  const double* hh = reinterpret_cast<const double*>(host.data());
+  const long long* hf = reinterpret_cast<const long long*>(hh + steps);
+  const int* hi = reinterpret_cast<const int*>(hf + nprob);
+  const int* hj = hi + steps;
+  for (int p = 0; p < nprob; ++p) {
+    if (hf[p] >= 0)
+      return fail(SCDE_EARG, "hclust: problem %d: non-finite distance at row %lld, column %lld (1-based)", p,
+                  hf[p] % n[p] + 1, hf[p] / n[p] + 1);
+    if (hf[p] != -1)
+      return fail(SCDE_EINTERNAL, "hclust: problem %d: no pair to merge at step %lld", p, -2 - hf[p]);
+  }
+  size_t so = 0, oo = 0;
+  for (int p = 0; p < nprob; ++p) {
+    hclust_encode(n[p], hi + so, hj + so, hh + so, method, merge + 2 * so, height + so, order + oo);
+    so += (size_t)n[p] - 1;
+    oo += (size_t)n[p];
+  }
+  return SCDE_OK;
+}
+
+static int hclust_check(const void* d, int64_t ld, int n, int method, const void* merge, const void* height,
+                        const void* order) {
+  if (!d || !merge || !height || !order) return fail(SCDE_EARG, "null argument");
+  if (n < 2) return fail(SCDE_EARG, "hclust: at least 2 objects are needed (n = %d)", n);
+  if (ld < n) return fail(SCDE_EARG, "hclust: ld must be at least n");
+  if (method < 0 || method > 5)
+    return fail(SCDE_EARG, "hclust: unknown method code %d (0 ward.D, 1 ward.D2, 2 single, 3 complete, 4 average, "
+                "5 mcquitty)", method);
+  return SCDE_OK;
+}
+
+int scde_hclust_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, int method, int* merge, double* height,
+                    int* order) {
+  FORK_GUARD();
+  RCHK(hclust_check(d_dev, ld, n, method, merge, height, order));
+  const int64_t off = 0;
+  return hclust_run(ctx, 1, d_dev, &off, &ld, &n, method, merge, height, order);
+}
+
+int scde_hclust_host(scde_ctx* ctx, const double* d, int64_t ld, int n, int method, int* merge, double* height,
+                     int* order) {
+  FORK_GUARD();
+  RCHK(hclust_check(d, ld, n, method, merge, height, order));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  if (ctx->hc_in.ensure(sizeof(double) * (size_t)n * n) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "hclust: out of memory: the matrix needs %zu bytes of device memory",
+                sizeof(double) * (size_t)n * n);
+  }
+  RCHK(dist_put(ctx, ctx->hc_in, d, ld, n, n));
+  const int64_t off = 0, ldn = n;
+  const int rc = hclust_run(ctx, 1, ctx->hc_in.as<double>(), &off, &ldn, &n, method, merge, height, order);
+  if (sizeof(double) * (size_t)n * n > ((size_t)1 << 30)) ctx->hc_in.release();
+  return rc;
+}
+
+int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int* n,
+                          int method, int* merge, double* height, int* order) {
+  FORK_GUARD();
+  if (nprob < 0) return fail(SCDE_EARG, "hclust: nprob must not be negative");
+  if (nprob == 0) return SCDE_OK;
+  if (!off || !n) return fail(SCDE_EARG, "null argument");
+  std::vector<int64_t> ldv(nprob);
+  for (int p = 0; p < nprob; ++p) {
+    if (off[p] < 0) return fail(SCDE_EARG, "hclust: problem %d: negative offset", p);
+    RCHK(hclust_check(d_dev, n[p], n[p], method, merge, height, order));
+    ldv[p] = n[p];
+  }
+  return hclust_run(ctx, nprob, d_dev, off, ldv.data(), n, method, merge, height, order);
+}
+
+// 1 - cor of the columns of a resident nrow x ncol matrix, into a resident ncol x ncol matrix
+// (k_matcorr with itself, then 1 - x): pagoda.gene.clusters' distance without a host visit.
+int scde_cor_distance_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev) {
+  FORK_GUARD();
+  if (!x_dev || !out_dev) return fail(SCDE_EARG, "null argument");
+  if (nrow < 1 || ncol < 1) return fail(SCDE_EARG, "bad dimensions");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  HCHK(ctx->pg_d.ensure(sizeof(double) * 4 * (size_t)ncol));
+  HCHK(launch_matcorr(x_dev, nrow, ncol, x_dev, ncol, ctx->pg_d.as<double>(), out_dev, ctx->stream));
+  HCHK(launch_one_minus(out_dev, ncol, ctx->stream));
+  return ctx->sync();
 }
 }  // extern "C"
 

@@ -424,4 +424,26 @@ hipError_t launch_wcorr_gram(const double* X, const double* U, long long ld, int
 hipError_t launch_recip_corr(const double* X, const double* F, int N, int C, const double* cellp, int sq, double k,
                              double* out, hipStream_t s);
 
+// ---- hierarchical clustering (hclust.hip; the contract is in include/scde_hip.h).
+// One problem of a launch: the n x n column-major matrix at src + src_off (leading dimension
+// ld, strict lower triangle read), its workspace of hclust_ws_bytes(n) at ws + ws_off (bytes, a
+// multiple of 256), its n - 1 raw steps at element out_off of oi / oj / oh.
+struct HclustProblem {
+  long long src_off, ld, ws_off, out_off;
+  int n;
+};
+size_t hclust_ws_bytes(int n);
+// one workgroup per problem; method 0..5 (ward.D, ward.D2, single, complete, average, mcquitty).
+// Step s of a problem merged slots oi[s] < oj[s] at oh[s] (ward.D2: the squared height).
+// flag[p]: -1 done; >= 0 the first non-finite pair, column j * n + row i (no steps written);
+// <= -2 an inconsistent neighbour cache at step -2 - flag (an internal error)
+hipError_t launch_hclust(const double* d, const HclustProblem* probs, int nprob, int method, char* ws, int* oi,
+                         int* oj, double* oh, long long* flag, hipStream_t s);
+// x <- 1 - x over an n x n matrix, the diagonal exactly 0 (a correlation matrix into a distance
+// matrix, in place)
+hipError_t launch_one_minus(double* x, long long n, hipStream_t s);
+// R's merge ((n - 1) x 2 column-major), height and order from the raw steps (host)
+void hclust_encode(int n, const int* si, const int* sj, const double* sh, int method, int* merge, double* height,
+                   int* order);
+
 }  // namespace scde
