@@ -285,7 +285,13 @@ int scde_posteriors_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngene
  * maximum.  Outputs (host): modes (1 [+ nbatch]) x ngenes (dataset-wide, then per level);
  * matw ngenes x ncells = 1 - mfp * sfp with mfp = scde.failure.probability at log(dataset
  * modes) and sfp = ppois(count - 1, exp(fail.r), lower.tail = FALSE) (1466-1474); bmatw (with
- * a batch) the same with each cell's level modes (1485-1506).  models: ncells x 12 col-major. */
+ * a batch) the same with each cell's level modes (1485-1506).  models: ncells x 12 col-major.
+ * The Poisson tail sfp is good for every exp(fail.r) in (0, inf] and every count: it is a
+ * series relative to the point mass at the count (in saddle-point form, never through
+ * exp(-exp(fail.r))), run until it converges -- about 9 sqrt(max(count, exp(fail.r))) terms
+ * where the two are close.  Against the regularised incomplete gamma function its relative
+ * error is about 1e-13 for exp(fail.r) up to 1e6, growing to about 3e-12 at 1e8; fail.r above
+ * 709.78 (exp overflows) gives sfp = 1 for every count. */
 int scde_pagoda_varnorm_weights_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
                                     const double* models, int local_theta, int square_logit_conc,
                                     const double* prior_x, int ngrid, int nboot, int n_cores, const int* batch_codes,

@@ -4161,6 +4161,7 @@ int scde_baileyWPCA(const double* mat, const double* matw, int n, int d, int npc
   if (nstarts <= 0) return fail(SCDE_EARG, "nstarts must be positive");
   const int K = std::min(npcs, d);
   if (K < 1) return fail(SCDE_EARG, "npcs must be positive");
+  if (K > wpca_max_k()) return fail(SCDE_EARG, "npcs must be in [1, %d]", wpca_max_k());  // before any device work
   scde_ctx* cx = nullptr;
   RCHK(default_ctx(&cx));
   HCHK(hipSetDevice(cx->device));

@@ -327,31 +327,55 @@ __global__ __launch_bounds__(256) void k_vn_modes(const double* __restrict__ jp,
   }
 }
 
+// log of the Poisson point mass e^-lambda lambda^x / x! (x >= 0, 0 < lambda < inf) in
+// Loader's saddle-point form, -D(x, lambda) - log(2 pi x) / 2 - delta(x), with the deviance
+// D = x log(x / lambda) + lambda - x through log1p of the exact difference and delta(x) =
+// log x! - log(sqrt(2 pi x) (x / e)^x) by its Stirling series (x >= 16) or from lgamma.  No
+// term is larger than the deviance itself, so the mass keeps ~1e-13 relative wherever it is
+// not negligible; -lambda + x log(lambda) - lgamma(x + 1) cancels thousands at x ~ lambda ~ 1000.
+__device__ double log_pois_mass(int x, double lambda) {
+  if (x == 0) return -lambda;
+  const double xd = (double)x;
+  const double dev = lambda - xd + xd * log1p((xd - lambda) / lambda);
+  double delta;
+  if (x >= 16) {
+    const double x2 = xd * xd;
+    delta = (1.0 / 12 - (1.0 / 360 - (1.0 / 1260 - (1.0 / 1680) / x2) / x2) / x2) / xd;
+  } else {
+    delta = lgamma(xd + 1.0) - (xd + 0.5) * log(xd) + xd - 0.91893853320467274178;  // log(2 pi) / 2
+  }
+  return -dev - 0.5 * log(6.28318530717958647692 * xd) - delta;
+}
+
 // upper Poisson tail P(X >= c), X ~ Poisson(lambda): R's ppois(c - 1, lambda, lower.tail =
-// FALSE) = pgamma(lambda, c) (nmath ppois_raw).  c <= 0: 1.  Otherwise the first term
-// e^-lambda lambda^c / c! times sum_j lambda^j / ((c+1)...(c+j)), summed until it stops
-// changing (lambda <= c: terms fall at least geometrically); for lambda > c the complement of
-// the lower sum.
+// FALSE) = pgamma(lambda, c) (nmath ppois_raw).  c <= 0: 1.  lambda <= c: the mass at c times
+// sum_j lambda^j / ((c+1)...(c+j)).  lambda > c: the complement of the lower sum, taken as the
+// mass at c - 1 (its largest term) times sum_j (c-1)...(c-j) / lambda^j, so that nothing
+// depends on e^-lambda, which underflows from lambda ~ 745.  Both series fall at least
+// geometrically and run until the sum stops changing (about 9 sqrt(max(c, lambda)) terms
+// when c ~ lambda).  lambda = inf (fail.r > 709.78): 1.
 __device__ double pois_upper(int c, double lambda) {
   if (c <= 0) return 1.0;
   if (!(lambda > 0.0)) return lambda == 0.0 ? 0.0 : NAN;
+  if (isinf(lambda)) return 1.0;
   if (lambda <= (double)c) {
-    const double lt = -lambda + c * log(lambda) - lgamma((double)c + 1.0);
     double term = 1.0, s = 1.0;
-    for (int j = 1; j < 10000; ++j) {
+    for (double j = 1;; j += 1) {
       term *= lambda / ((double)c + j);
       const double s1 = s + term;
       if (s1 == s) break;
       s = s1;
     }
-    return exp(lt) * s;
+    return exp(log_pois_mass(c, lambda)) * s;
   }
-  double term = exp(-lambda), s = term;  // P(X <= c - 1)
-  for (int k = 1; k < c; ++k) {
-    term *= lambda / k;
-    s += term;
+  double term = 1.0, s = 1.0;  // P(X <= c - 1) / P(X = c - 1)
+  for (int k = c - 1; k > 0; --k) {
+    term *= (double)k / lambda;
+    const double s1 = s + term;
+    if (s1 == s) break;
+    s = s1;
   }
-  return 1.0 - s;
+  return 1.0 - exp(log_pois_mass(c - 1, lambda)) * s;
 }
 
 // matw[g, j] = 1 - mfp[g, j] * sfp[g, j] for the cells j of one call (R/functions.R:1466-1474,
