@@ -503,6 +503,59 @@ int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const i
  * for scde_hclust_dev. */
 int scde_cor_distance_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev);
 
+/* ---------------------------------------------------------------- pagoda.gene.clusters' random rounds
+ * The null model of pagoda.gene.clusters (R/functions.R:2131-2192): per round i, set.seed(i), a
+ * genes x cells matrix of rnorm, winsorize, drop the genes that fail the keep rule, 1 - cor,
+ * hclust, cutree, and per cluster the PC1 variance.  The pieces below work on a round matrix
+ * resident in HBM as ncells x ngenes column-major (a gene's cells contiguous), the layout
+ * scde_cor_distance_dev takes; scde_amd/cluster.py chains them.  ctx may be NULL. */
+
+/* R's rnorm stream (RNGkind "Mersenne-Twister", "Inversion"), host side, on scde_r_set_seed's
+ * state, which is advanced in place.  scde_r_norm_rand: n values of norm_rand(), i.e.
+ *   u = unif_rand(); u = (int)(134217728 * u) + unif_rand(); qnorm(u / 134217728)
+ * (two uniforms per normal).  scde_r_mt_words: the n raw tempered 32-bit outputs that the next n
+ * unif_rand() calls would scale (MT_genrand before its * 2.3283064365386963e-10). */
+int scde_r_norm_rand(uint32_t* state, int64_t n, double* out);
+int scde_r_mt_words(uint32_t* state, int64_t n, uint32_t* out);
+/* matrix(rnorm(ngenes * ncells), nrow = ngenes) from 2 * ngenes * ncells raw words (host): draw t
+ * uses words 2 t and 2 t + 1 and is gene t % ngenes, cell t / ngenes; out_dev[g * ncells + c].
+ * The scaling, unif_rand's fix-up of 0 and 1, the 2^27 combination and qnorm (AS241) run on
+ * the device in the host's arithmetic; only qnorm's log and sqrt may round differently. */
+int scde_rnorm_matrix_dev(scde_ctx* ctx, const uint32_t* words, int ngenes, int ncells, double* out_dev);
+
+/* winsorize.matrix per gene on a resident matrix: bit-equal to scde_winsorizeMatrix of the
+ * genes x cells matrix.  ncells <= 8192, or round(ncells * trim) <= 32, else SCDE_EARG; out_dev
+ * must not be x_dev. */
+int scde_winsorize_dev(scde_ctx* ctx, const double* x_dev, int ncells, int ngenes, double trim, double* out_dev);
+/* The random rounds' keep rule which(abs(sum(diff(abs(x)))) > 0) (R/functions.R:2146; not the
+ * observed half's sum(abs(diff(x)))): per gene the differences |x[k + 1]| - |x[k]|, each rounded
+ * to double, are summed in cell order in double-double (R's long-double sum); keep[g] (host,
+ * ngenes ints) is 1 iff the rounded sum is not zero.  ncells < 2 is SCDE_EARG (an empty diff
+ * drops every gene). */
+int scde_keep_absdiff_dev(scde_ctx* ctx, const double* x_dev, int ncells, int ngenes, int* keep);
+/* out_dev column j = x_dev column cols[j] (nrow rows; x_dev has ncol columns; cols: host, nsel
+ * entries in [0, ncol)); the buffers must not overlap. */
+int scde_gather_cols_dev(scde_ctx* ctx, const double* x_dev, int nrow, int64_t ncol, const int* cols, int nsel,
+                         double* out_dev);
+
+/* Squared largest singular value, batched (csrc/sigma1.hip).  x_dev: ncells x ngenes resident
+ * matrix; problem p is the block M of its columns idx[off[p] .. off[p + 1]) (host lists, any
+ * order, at least one column); out[p] (host) = sigma_1(M)^2.  pagoda.gene.clusters' value
+ * pcaMethods::sDev(pca(m[, ii], nPcs = 1, center = FALSE))^2 is out[p] / max(1, ncells - 1).
+ * One launch, one workgroup per problem: the Gram matrix of the smaller side on the FP64 matrix
+ * cores, Householder tridiagonalisation, Sturm bisection of the largest eigenvalue down to
+ * adjacent doubles.  The result is bit-repeatable and depends on the problem alone (no atomics;
+ * not on the launch, nor on the other problems); it is exactly 0 for an all-zero block, the sum
+ * of squares for one column, NaN when the block holds a non-finite value.  Column indices are
+ * checked on the host (SCDE_EARG naming the problem) and again on the device before any is used.
+ * SCDE_EHIP "out of memory", before the launch, when the workspace (sum over problems of
+ * min(columns, ncells)^2 + O(min) doubles) cannot be allocated. */
+int scde_sigma1sq_batch_dev(scde_ctx* ctx, const double* x_dev, int ncells, int64_t ngenes, int nprob,
+                            const int64_t* off, const int* idx, double* out);
+
+/* Free and total bytes of the context's device (hipMemGetInfo). */
+int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ from .api import (Context, DeviceCounts, RatioPosterior, ScdeError, bh_cz, calcu
                   marginals, matSlideMult, quick_distribution_summary, ratio_columns, scde_expression_difference,
                   scde_posteriors, set_rand)
 from .cluster import (HClust, cutree, hclust, hclust_batch, pagoda_cluster_cells,  # noqa: F401
-                      pagoda_gene_clusters_observed)
+                      pagoda_gene_cluster_samples, pagoda_gene_clusters, pagoda_gene_clusters_observed)
 from .distance import (direct_dropout_distance, mode_relative_distance, reciprocal_distance,  # noqa: F401
                        weighted_correlation)
 from .prior import expression_prior  # noqa: F401

@@ -30,6 +30,8 @@ EXPORTS = [
     "scde_wcorr_sep_dev", "scde_wcorr_sep_host", "scde_reciprocal_corr_dev", "scde_reciprocal_corr_host",
     "scde_mode_fail_corr_dev", "scde_mode_fail_corr_host", "scde_direct_corr_dev", "scde_direct_corr_host",
     "scde_hclust_host", "scde_hclust_dev", "scde_hclust_batch_dev", "scde_cor_distance_dev",
+    "scde_r_norm_rand", "scde_r_mt_words", "scde_rnorm_matrix_dev", "scde_winsorize_dev", "scde_keep_absdiff_dev",
+    "scde_gather_cols_dev", "scde_sigma1sq_batch_dev", "scde_dev_mem_info",
 ]
 
 
@@ -135,6 +137,13 @@ def lib():
     L.scde_hclust_host.argtypes = L.scde_hclust_dev.argtypes = [P, P, i64, i, i, P, P, P]
     L.scde_hclust_batch_dev.argtypes = [P, i, P, P, P, i, P, P, P]
     L.scde_cor_distance_dev.argtypes = [P, P, i, i, P]
+    L.scde_r_norm_rand.argtypes = L.scde_r_mt_words.argtypes = [P, i64, P]
+    L.scde_rnorm_matrix_dev.argtypes = [P, P, i, i, P]
+    L.scde_winsorize_dev.argtypes = [P, P, i, i, d, P]
+    L.scde_keep_absdiff_dev.argtypes = [P, P, i, i, P]
+    L.scde_gather_cols_dev.argtypes = [P, P, i, i64, P, i, P]
+    L.scde_sigma1sq_batch_dev.argtypes = [P, P, i, i64, i, P, P, P]
+    L.scde_dev_mem_info.argtypes = [P, P, P]
     _lib = L
     return L
 

@@ -8,6 +8,10 @@ PAGODA steps that consume a distance matrix.
   * ``pagoda_cluster_cells``               R/functions.R:2641-2678
   * ``pagoda_gene_clusters_observed``      R/functions.R:2060-2121, the observed half of
                                            ``pagoda.gene.clusters``
+  * ``pagoda_gene_cluster_samples``        R/functions.R:2131-2192, its randomised half (the null
+                                           model's sampled PC1 variances), rounds batched
+  * ``pagoda_gene_clusters``               the whole function: both halves and the scoring of
+                                           R/functions.R:2196-2211 (``scde_amd/rmt.py``)
 
 Only the strict lower triangle of a distance matrix is read (what ``as.dist`` reads), and every
 value there must be finite.  The pair merged at each step is the lexicographic minimum of
@@ -286,3 +290,246 @@ def pagoda_gene_clusters_observed(varinfo, trim=None, n_clusters=150, n_starts=1
     if return_details:
         out.update(distance=dist, clustering=hc, genes=[names[i] for i in vi])
     return out
+
+
+def _ptr(base, byte_off):
+    return ctypes.c_void_p(base.value + int(byte_off))
+
+
+def _mt_words(seed, n):
+    """The first n raw Mersenne-Twister words after ``set.seed(seed)`` (host; releases the GIL)."""
+    state = np.zeros(625, np.uint32)
+    words = np.empty(n, np.uint32)
+    L = lib()
+    check(L.scde_r_set_seed(int(seed), api._p(state)))
+    check(L.scde_r_mt_words(api._p(state), n, api._p(words)))
+    return words
+
+
+def dev_mem_info(ctx: api.Context | None = None):
+    """(free, total) bytes of the context's device."""
+    ctx = ctx or api.default_context()
+    free, total = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().scde_dev_mem_info(ctx.handle, ctypes.byref(free), ctypes.byref(total)))
+    return free.value, total.value
+
+
+def _hclust_ws_bytes(n):
+    return 8 * n * n + 25 * n + 256  # csrc/hclust.hip's hclust_ws_bytes: the n^2 working copy and O(n) lists
+
+
+def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples=60, method="ward.D",
+                                secondary_correlation=False, rounds_per_batch=None, matrices=None,
+                                return_details=False, timings=None, ctx: api.Context | None = None):
+    """The randomised half of ``pagoda.gene.clusters`` (R/functions.R:2131-2192), n.cores = 1:
+    for round i = 1..n_samples, ``set.seed(i)``, ``matrix(rnorm(ngenes * n_cells), nrow = ngenes)``,
+    winsorize (``trim`` > 0), keep the genes with ``abs(sum(diff(abs(x)))) > 0``, cluster them on
+    1 - cor (optionally the correlation of that distance again), cut into ``n_clusters`` and take
+    per cluster ``pcaMethods::sDev(pca(m[, ii], nPcs = 1, center = FALSE))^2``, read as
+    sigma_1^2 / max(1, n_cells - 1) (from memory of pcaMethods; not checked against it).
+
+    Returns {"n", "var", "round"}: one row per cluster, rounds in order 1..n_samples and within a
+    round in cluster-label order (R's ``tapply`` order).
+
+    Every step runs on matrices resident in HBM.  Rounds are processed in batches: the distance
+    matrices of a batch are packed in one buffer and clustered in one launch (one workgroup per
+    round), and the PC1 variances of all clusters of all its rounds come from one launch.
+    ``rounds_per_batch=None`` sizes the batch so that what grows with it -- per round its distance
+    matrix (twice with ``secondary_correlation``), the clustering's n^2 workspace and step lists,
+    the round matrix and the PC1 kernel's workspace (at most genes x min(genes, cells) doubles) --
+    and the three round-sized staging buffers take at most half of the device memory that is
+    free; the batch size changes no bit of the result.  The host draws round i + 1's
+    Mersenne-Twister words while the device works on round i.
+
+    ``matrices`` (a list of genes x cells arrays) replaces the drawn matrices (``n_samples`` is
+    then its length).  With ``return_details`` the result gains "details": per round {"kept" (gene
+    indices), "matrix" (the winsorized kept genes x cells, read back), "distance" (read back),
+    "clustering", "labels"}.  ``timings`` (a dict, for tools/bench_gene_clusters.py) receives the
+    host-clock seconds spent inside each group of library calls, every one of which ends in a
+    stream synchronise: "draw", "winsorize" (with the keep rule and the gather), "distance",
+    "clustering", "sigma1"."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    code = _method_code(method)
+    ngenes, n_cells, n_clusters = int(ngenes), int(n_cells), int(n_clusters)
+    if matrices is not None:
+        matrices = [np.ascontiguousarray(m, dtype=np.float64) for m in matrices]
+        n_samples = len(matrices)
+        if any(m.shape != (ngenes, n_cells) for m in matrices):
+            raise ValueError(f"every matrix must be {ngenes} x {n_cells} (genes x cells)")
+    n_samples = int(n_samples)
+    if ngenes < 2:
+        raise ValueError("at least 2 genes are needed")
+    if n_cells < 2:
+        raise ValueError("at least 2 cells are needed: with one cell diff() is empty and every gene is dropped")
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1")
+    if not 1 <= n_clusters <= ngenes:
+        raise ValueError(f"n_clusters must be in [1, {ngenes}]")
+    if not 0 <= trim < 1:
+        raise ValueError("trim must be in [0, 1)")
+    ctx = ctx or api.default_context()
+    L = lib()
+    msz = 8 * ngenes * n_cells  # one round matrix
+    dsz = 8 * ngenes * ngenes   # one distance matrix
+    if rounds_per_batch is None:
+        free, _ = dev_mem_info(ctx)
+        per_round = (dsz * (2 if secondary_correlation else 1) + _hclust_ws_bytes(ngenes) + 16 * ngenes + msz
+                     + 8 * (ngenes + 4) * min(ngenes, n_cells) + 256)
+        rounds_per_batch = (free // 2 - 3 * msz) // per_round  # raw, wz and the library's word buffer
+    B = int(max(1, min(int(rounds_per_batch), n_samples)))
+    tm = timings if timings is not None else {}
+    for k in ("draw", "winsorize", "distance", "clustering", "sigma1"):
+        tm.setdefault(k, 0.0)
+
+    def timed(key, t0):
+        t1 = time.perf_counter()
+        tm[key] += t1 - t0
+        return t1
+
+    bufs = []
+
+    def dev(nbytes):
+        p = ctypes.c_void_p()
+        check(L.scde_dev_alloc(ctx.handle, max(int(nbytes), 8), ctypes.byref(p)))
+        bufs.append(p)
+        return p
+
+    out_n, out_var, out_round, details = [], [], [], []
+    nwords = 2 * ngenes * n_cells
+    pool = ThreadPoolExecutor(max_workers=1) if matrices is None else None
+    try:
+        nxt = pool.submit(_mt_words, 1, nwords) if pool else None
+        raw = dev(msz)          # a round's matrix as drawn (or given)
+        wz = dev(msz)           # the same winsorized, every gene still in place
+        xw = dev(B * msz)       # the batch's winsorized, kept matrices: n_cells x (B * ngenes)
+        gd = dev(B * dsz)       # the batch's distance matrices, round r at element r * ngenes^2
+        gd2 = dev(B * dsz) if secondary_correlation else None
+        for b0 in range(0, n_samples, B):
+            nb = min(B, n_samples - b0)
+            nk = np.zeros(nb, np.int32)
+            kept = []
+            for r in range(nb):
+                i = b0 + r + 1  # the round, R's set.seed(i)
+                t0 = time.perf_counter()
+                if matrices is None:
+                    words = nxt.result()
+                    nxt = pool.submit(_mt_words, i + 1, nwords) if i < n_samples else None
+                    check(L.scde_rnorm_matrix_dev(ctx.handle, api._p(words), ngenes, n_cells, raw))
+                else:
+                    check(L.scde_h2d(ctx.handle, raw, api._p(matrices[i - 1]), msz))
+                t0 = timed("draw", t0)
+                slot = _ptr(xw, r * msz)
+                check(L.scde_winsorize_dev(ctx.handle, raw, n_cells, ngenes, float(trim), wz))
+                keep = np.zeros(ngenes, np.int32)
+                check(L.scde_keep_absdiff_dev(ctx.handle, wz, n_cells, ngenes, api._p(keep)))
+                vi = np.nonzero(keep)[0].astype(np.int32)
+                # A round drops a gene when its first and last cell were clipped to the same bound and
+                # the rounded differences cancel exactly (about one round in two at 120 x 24; DESIGN.md
+                # section 4.8).  The kept columns go to the round's slot in one gather, which is a plain
+                # copy in the rounds that keep every gene.
+                if len(vi) < 2 or n_clusters > len(vi):
+                    raise ValueError(f"round {i}: {len(vi)} genes pass the keep rule, fewer than "
+                                     f"{max(2, n_clusters)}")
+                check(L.scde_gather_cols_dev(ctx.handle, wz, n_cells, ngenes, api._p(vi), len(vi), slot))
+                kept.append(vi)
+                nk[r] = len(vi)
+                t0 = timed("winsorize", t0)
+                dr = _ptr(gd, r * dsz)
+                check(L.scde_cor_distance_dev(ctx.handle, slot, n_cells, int(nk[r]), dr))
+                if secondary_correlation:
+                    check(L.scde_cor_distance_dev(ctx.handle, dr, int(nk[r]), int(nk[r]), _ptr(gd2, r * dsz)))
+                timed("distance", t0)
+            t0 = time.perf_counter()
+            dist_buf = gd2 if secondary_correlation else gd
+            off = np.arange(nb, dtype=np.int64) * (ngenes * ngenes)
+            steps = int((nk - 1).sum())
+            merge = np.zeros(2 * steps, np.int32)
+            height = np.zeros(steps)
+            order = np.zeros(int(nk.sum()), np.int32)
+            check(L.scde_hclust_batch_dev(ctx.handle, nb, dist_buf, api._p(off), api._p(nk), code, api._p(merge),
+                                          api._p(height), api._p(order)))
+            t0 = timed("clustering", t0)
+            idx, cnt, so, oo = [], [], 0, 0
+            for r in range(nb):
+                m = int(nk[r]) - 1
+                hc = HClust(merge[2 * so:2 * (so + m)].reshape((m, 2), order="F"), height[so:so + m],
+                            order[oo:oo + m + 1], method)
+                so += m
+                oo += m + 1
+                lab = cutree(hc, k=n_clusters)
+                idx.append((np.argsort(lab, kind="stable") + r * ngenes).astype(np.int32))  # label, then gene order
+                cnt.append(np.bincount(lab, minlength=n_clusters + 1)[1:])
+                if return_details:
+                    dist = np.zeros((m + 1, m + 1), order="F")
+                    check(L.scde_d2h(ctx.handle, api._p(dist), _ptr(dist_buf, r * dsz), dist.nbytes))
+                    mk = np.zeros((m + 1, n_cells))  # genes x cells, C order: the resident layout
+                    check(L.scde_d2h(ctx.handle, api._p(mk), _ptr(xw, r * msz), mk.nbytes))
+                    details.append({"kept": kept[r], "matrix": mk, "distance": dist, "labels": lab,
+                                    "clustering": HClust(hc.merge.copy(order="F"), hc.height.copy(), hc.order.copy(),
+                                                         method)})
+            idx = np.ascontiguousarray(np.concatenate(idx))
+            cnt = np.concatenate(cnt).astype(np.int64)
+            poff = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+            s1 = np.zeros(len(cnt))
+            t0 = time.perf_counter()
+            check(L.scde_sigma1sq_batch_dev(ctx.handle, xw, n_cells, nb * ngenes, len(cnt), api._p(poff), api._p(idx),
+                                            api._p(s1)))
+            timed("sigma1", t0)
+            out_n.append(cnt.astype(np.int32))
+            out_var.append(s1 / max(1, n_cells - 1))
+            out_round.append(np.repeat(np.arange(b0 + 1, b0 + nb + 1, dtype=np.int32), n_clusters))
+    except BaseException:
+        if pool:
+            pool.shutdown(wait=True, cancel_futures=True)
+        for p in bufs:  # (a failure to free must not replace the error on its way out)
+            L.scde_dev_free(ctx.handle, p)
+        raise
+    if pool:
+        pool.shutdown(wait=True)
+    for p in bufs:
+        check(L.scde_dev_free(ctx.handle, p))
+    out = {"n": np.concatenate(out_n), "var": np.concatenate(out_var), "round": np.concatenate(out_round)}
+    if return_details:
+        out["details"] = details
+    return out
+
+
+def pagoda_gene_clusters(varinfo, trim=None, n_clusters=150, n_samples=60, n_internal_shuffles=0, n_starts=10,
+                         n_components=1, method="ward.D", secondary_correlation=False, n_cells=None, old_results=None,
+                         seed=1, ctx: api.Context | None = None):
+    """``pagoda.gene.clusters`` (R/functions.R:2058-2237; n.cores = 1, no plot, no ``show.random``):
+    the observed clusters (``pagoda_gene_clusters_observed``) scored against the null model of
+    ``pagoda_gene_cluster_samples`` on ``nrow(varinfo$mat)`` x ``n_cells`` random matrices
+    (``n_cells`` defaults to the cells of ``varinfo``).
+
+    Returns the reference's list: {"clusters", "cl.goc", "trim"} as the observed half gives them;
+    "varm": {"n", "var", "round", "pm", "pv", "varst"}; "clvlm": the fit ``var ~ 0 + pm + n``
+    ({"coefficients", "fitted.values", "residuals"}); "tci": {round: row of ``varm`` with the
+    round's first maximum ``varst``}, rows 0-based (R's are 1-based); "xf": the Gumbel maximum-
+    likelihood fit of ``varst`` {"location", "scale"} (``scde_amd.rmt``).
+
+    ``old_results`` reuses its "clusters" / "cl.goc" and, when it has one, its "varm" (n, var,
+    round), as R/functions.R:2074-2129 do; with a "varm" no device work is done."""
+    from . import rmt
+    _method_code(method)
+    ngenes, ncol = np.asarray(varinfo["mat"]).shape
+    if trim is None:
+        trim = 3.1 / ncol
+    n_cells = ncol if n_cells is None else int(n_cells)
+    if old_results is not None:
+        clusters, goc = old_results["clusters"], old_results["cl.goc"]
+    else:
+        obs = pagoda_gene_clusters_observed(varinfo, trim=trim, n_clusters=n_clusters, n_starts=n_starts,
+                                            n_components=n_components, n_internal_shuffles=n_internal_shuffles,
+                                            method=method, secondary_correlation=secondary_correlation, seed=seed,
+                                            ctx=ctx)
+        clusters, goc = obs["clusters"], obs["cl.goc"]
+    if old_results is not None and old_results.get("varm") is not None:
+        varm = {k: np.asarray(old_results["varm"][k]) for k in ("n", "var", "round")}
+    else:
+        varm = pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=n_clusters, n_samples=n_samples,
+                                           method=method, secondary_correlation=secondary_correlation, ctx=ctx)
+    varm, clvlm, tci = rmt.score_varm(varm, n_cells)
+    xf = rmt.gumbel_fit(varm["varst"])
+    return {"clusters": clusters, "xf": xf, "tci": tci, "cl.goc": goc, "varm": varm, "clvlm": clvlm, "trim": trim}

@@ -264,6 +264,9 @@ struct scde_ctx {
   // hierarchical clustering (hclust.hip): a host matrix staged, the problems' workspaces, the
   // problem descriptors, the raw steps (oi, oj, oh, flags)
   Buf hc_in, hc_ws, hc_prob, hc_out;
+  // the random rounds of pagoda.gene.clusters: raw twister words, keep flags / column lists,
+  // sigma1's problem lists, workspace and results
+  Buf gr_raw, gr_int, gr_prob, gr_ws, gr_out;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters
@@ -582,6 +585,7 @@ struct scde_ctx {
                  &pg_a,     &pg_b,       &pg_c,    &pg_d,      &pg_e,      &counts_in, &w8,
                  &ds_x,     &ds_u,       &ds_f,    &ds_p,      &ds_x0,     &ds_cell,   &ds_jpm,   &ds_out,
                  &hc_in,    &hc_ws,      &hc_prob, &hc_out,
+                 &gr_raw,   &gr_int,     &gr_prob, &gr_ws,     &gr_out,
                  &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &ellw,  &excd, &gdone};
     for (Buf* b : wp) b->release();
     for (auto& u : us) u.release();
@@ -3808,7 +3812,7 @@ int scde_r_set_seed(uint32_t seed, uint32_t* state) {
   return SCDE_OK;
 }
 
-static double r_mt_genrand(uint32_t* st) {
+static uint32_t r_mt_word(uint32_t* st) {
   static const uint32_t mag01[2] = {0x0u, 0x9908b0dfu};
   uint32_t* mt = st + 1;
   int mti = (int)st[0];
@@ -3833,8 +3837,10 @@ static double r_mt_genrand(uint32_t* st) {
   y ^= (y << 15) & 0xefc60000u;
   y ^= (y >> 18);
   st[0] = (uint32_t)mti;
-  return (double)y * 2.3283064365386963e-10;
+  return y;
 }
+
+static double r_mt_genrand(uint32_t* st) { return (double)r_mt_word(st) * 2.3283064365386963e-10; }
 
 static double r_unif_rand(uint32_t* st) {
   const double i2_32m1 = 2.328306437080797e-10;
@@ -3847,6 +3853,24 @@ static double r_unif_rand(uint32_t* st) {
 int scde_r_unif_rand(uint32_t* state, int64_t n, double* out) {
   if (!state || (n > 0 && !out)) return fail(SCDE_EARG, "null argument");
   for (int64_t i = 0; i < n; ++i) out[i] = r_unif_rand(state);
+  return SCDE_OK;
+}
+
+int scde_r_mt_words(uint32_t* state, int64_t n, uint32_t* out) {
+  if (!state || (n > 0 && !out)) return fail(SCDE_EARG, "null argument");
+  for (int64_t i = 0; i < n; ++i) out[i] = r_mt_word(state);
+  return SCDE_OK;
+}
+
+// norm_rand(), INVERSION (src/nmath/snorm.c): two uniforms per normal, 2^27 the "BIG" there
+int scde_r_norm_rand(uint32_t* state, int64_t n, double* out) {
+  if (!state || (n > 0 && !out)) return fail(SCDE_EARG, "null argument");
+  const double big = 134217728.0;
+  for (int64_t i = 0; i < n; ++i) {
+    double u = r_unif_rand(state);
+    u = (double)(int)(big * u) + r_unif_rand(state);
+    out[i] = qnorm_host(u / big, true);
+  }
   return SCDE_OK;
 }
 
@@ -4593,6 +4617,135 @@ int scde_cor_distance_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol
   HCHK(launch_matcorr(x_dev, nrow, ncol, x_dev, ncol, ctx->pg_d.as<double>(), out_dev, ctx->stream));
   HCHK(launch_one_minus(out_dev, ncol, ctx->stream));
   return ctx->sync();
+}
+
+// ------------------------------------------------------------------ pagoda.gene.clusters' random rounds
+// (contract in scde_hip.h).  Arguments are checked before the GPU is touched.
+int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes) {
+  FORK_GUARD();
+  if (!free_bytes || !total_bytes) return fail(SCDE_EARG, "null argument");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  size_t f = 0, t = 0;
+  HCHK(hipMemGetInfo(&f, &t));
+  *free_bytes = (int64_t)f;
+  *total_bytes = (int64_t)t;
+  return SCDE_OK;
+}
+
+int scde_rnorm_matrix_dev(scde_ctx* ctx, const uint32_t* words, int ngenes, int ncells, double* out_dev) {
+  FORK_GUARD();
+  if (!words || !out_dev) return fail(SCDE_EARG, "null argument");
+  if (ngenes < 1 || ncells < 1) return fail(SCDE_EARG, "bad dimensions");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  RCHK(upload(ctx, ctx->gr_raw, words, sizeof(uint32_t) * 2 * (size_t)ngenes * ncells));
+  HCHK(launch_rnorm(ctx->gr_raw.as<uint32_t>(), ngenes, ncells, out_dev, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_winsorize_dev(scde_ctx* ctx, const double* x_dev, int ncells, int ngenes, double trim, double* out_dev) {
+  FORK_GUARD();
+  if (!x_dev || !out_dev) return fail(SCDE_EARG, "null argument");
+  if (x_dev == out_dev) return fail(SCDE_EARG, "winsorize: in place is not supported");
+  if (ngenes < 1 || ncells < 1) return fail(SCDE_EARG, "bad dimensions");
+  const int ntr = (int)std::round(ncells * trim);
+  if (ntr < 0 || ntr > ncells - 1)
+    return fail(SCDE_EARG, "winsorize: trim %g out of range for %d cells", trim, ncells);
+  int NP = 1;
+  while (NP < ncells) NP <<= 1;
+  if (NP > 8192 && ntr > 32) return fail(SCDE_EARG, "winsorize: more than 8192 cells need round(cells * trim) <= 32");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  if (ntr == 0)
+    HCHK(hipMemcpyAsync(out_dev, x_dev, sizeof(double) * (size_t)ncells * ngenes, hipMemcpyDeviceToDevice,
+                        ctx->stream));
+  else
+    HCHK(launch_winsorize_gc(x_dev, ncells, ngenes, ntr, out_dev, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_keep_absdiff_dev(scde_ctx* ctx, const double* x_dev, int ncells, int ngenes, int* keep) {
+  FORK_GUARD();
+  if (!x_dev || !keep) return fail(SCDE_EARG, "null argument");
+  if (ngenes < 1) return fail(SCDE_EARG, "bad dimensions");
+  if (ncells < 2)  // diff() of one value is empty: every gene would be dropped
+    return fail(SCDE_EARG, "keep rule: at least 2 cells are needed (ncells = %d)", ncells);
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  HCHK(ctx->gr_int.ensure(sizeof(int) * (size_t)ngenes));
+  HCHK(launch_keep_absdiff(x_dev, ncells, ngenes, ctx->gr_int.as<int>(), ctx->stream));
+  HCHK(hipMemcpyAsync(keep, ctx->gr_int.p, sizeof(int) * (size_t)ngenes, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_gather_cols_dev(scde_ctx* ctx, const double* x_dev, int nrow, int64_t ncol, const int* cols, int nsel,
+                         double* out_dev) {
+  FORK_GUARD();
+  if (!x_dev || !out_dev || (nsel > 0 && !cols)) return fail(SCDE_EARG, "null argument");
+  if (nrow < 1 || ncol < 1 || nsel < 0) return fail(SCDE_EARG, "bad dimensions");
+  for (int j = 0; j < nsel; ++j)
+    if (cols[j] < 0 || cols[j] >= ncol) return fail(SCDE_EARG, "gather: column %d of the list is %d", j, cols[j]);
+  if (nsel == 0) return SCDE_OK;
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  RCHK(upload(ctx, ctx->gr_int, cols, sizeof(int) * (size_t)nsel));
+  HCHK(launch_gather_cols(x_dev, nrow, ctx->gr_int.as<int>(), nsel, out_dev, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_sigma1sq_batch_dev(scde_ctx* ctx, const double* x_dev, int ncells, int64_t ngenes, int nprob,
+                            const int64_t* off, const int* idx, double* out) {
+  FORK_GUARD();
+  if (nprob < 0) return fail(SCDE_EARG, "sigma1sq: nprob must not be negative");
+  if (nprob == 0) return SCDE_OK;
+  if (!x_dev || !off || !idx || !out) return fail(SCDE_EARG, "null argument");
+  if (ncells < 1 || ngenes < 1) return fail(SCDE_EARG, "bad dimensions");
+  if (off[0] < 0) return fail(SCDE_EARG, "sigma1sq: negative offset");
+  std::vector<long long> po(2 * (size_t)nprob + 1);  // off[nprob + 1], then ws_off[nprob]
+  size_t wsd = 0;
+  for (int p = 0; p < nprob; ++p) {
+    const int64_t q = off[p + 1] - off[p];
+    if (q < 1) return fail(SCDE_EARG, "sigma1sq: problem %d has no columns", p);
+    for (int64_t t = off[p]; t < off[p + 1]; ++t)
+      if (idx[t] < 0 || idx[t] >= ngenes)
+        return fail(SCDE_EARG, "sigma1sq: problem %d: column index %d outside [0, %lld)", p, idx[t],
+                    (long long)ngenes);
+    po[p] = off[p];
+    po[nprob + 1 + p] = (long long)wsd;
+    wsd += sigma1_ws_doubles(q, ncells);
+  }
+  po[nprob] = off[nprob];
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  // the workspace comes first: a batch that does not fit fails here, before any launch
+  if (ctx->gr_ws.ensure(sizeof(double) * wsd) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "sigma1sq: out of memory: the workspace of %d problem(s) needs %zu bytes of device memory",
+                nprob, sizeof(double) * wsd);
+  }
+  const size_t nidx = (size_t)(off[nprob] - off[0]);
+  HCHK(ctx->gr_prob.ensure(sizeof(long long) * po.size() + sizeof(int) * nidx));
+  long long* d_off = ctx->gr_prob.as<long long>();
+  int* d_idx = reinterpret_cast<int*>(d_off + po.size());
+  for (int p = 0; p <= nprob; ++p) po[p] -= off[0];
+  HCHK(hipMemcpyAsync(d_off, po.data(), sizeof(long long) * po.size(), hipMemcpyHostToDevice, ctx->stream));
+  HCHK(hipMemcpyAsync(d_idx, idx + off[0], sizeof(int) * nidx, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(ctx->gr_out.ensure((sizeof(double) + sizeof(int)) * (size_t)nprob));
+  double* d_out = ctx->gr_out.as<double>();
+  int* d_flag = reinterpret_cast<int*>(d_out + nprob);
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_sigma1sq(x_dev, ncells, ngenes, nprob, d_off, d_idx, d_off + nprob + 1, ctx->gr_ws.as<double>(), d_out,
+                       d_flag, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  std::vector<int> hf(nprob);
+  HCHK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)nprob, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(hf.data(), d_flag, sizeof(int) * (size_t)nprob, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  if (sizeof(double) * wsd > ((size_t)1 << 30)) ctx->gr_ws.release();
+  for (int p = 0; p < nprob; ++p)
+    if (hf[p] != 0) return fail(SCDE_EINTERNAL, "sigma1sq: problem %d: a column index failed the device check", p);
+  return SCDE_OK;
 }
 }  // extern "C"
 

@@ -446,4 +446,23 @@ hipError_t launch_one_minus(double* x, long long n, hipStream_t s);
 void hclust_encode(int n, const int* si, const int* sj, const double* sh, int method, int* merge, double* height,
                    int* order);
 
+// ---- the randomised rounds of pagoda.gene.clusters (rnorm.hip, pagoda.hip, sigma1.hip; contract
+// in include/scde_hip.h).  Round matrices are ncells x ngenes column-major (a gene contiguous).
+// R's norm_rand() (INVERSION) from raw Mersenne-Twister outputs, two per normal: draw t goes to
+// gene t % ngenes, cell t / ngenes
+hipError_t launch_rnorm(const uint32_t* raw, int ngenes, int ncells, double* out, hipStream_t s);
+// winsorize every gene of an ncells x ngenes matrix (launch_winsorize's kernels on this layout)
+hipError_t launch_winsorize_gc(const double* x, int ncells, int ngenes, int ntr, double* out, hipStream_t s);
+// keep[g] = (sum over cells of the rounded |x[k + 1]| - |x[k]|, in double-double) != 0
+hipError_t launch_keep_absdiff(const double* x, int ncells, int ngenes, int* keep, hipStream_t s);
+// out column j = x column cols[j] (nrow rows each)
+hipError_t launch_gather_cols(const double* x, int nrow, const int* cols, int ncols, double* out, hipStream_t s);
+// Squared largest singular value of the ncells x |cols| blocks of x.  Problem p: columns
+// idx[off[p] .. off[p + 1]), a workspace of sigma1_ws_doubles(.) doubles at ws + ws_off[p].
+// out[p]: the value; flag[p]: 0, or 1 when a column index was outside [0, ngenes) (out[p] is NaN)
+size_t sigma1_ws_doubles(long long ncols, int ncells);
+hipError_t launch_sigma1sq(const double* x, int ncells, long long ngenes, int nprob, const long long* off,
+                           const int* idx, const long long* ws_off, double* ws, double* out, int* flag,
+                           hipStream_t s);
+
 }  // namespace scde

@@ -49,8 +49,9 @@ __device__ __forceinline__ void tri_pair(long long q, int n, int& i, int& j) {
 // ---- winsorizeMatrix: one workgroup per row (rows spread so consecutive rows share an
 // XCD and its L2: row = (b % 8) * ceil(k / 8) + b / 8).  The row (stride k in R's
 // column-major layout) is bitonic-sorted in LDS as (value, index) pairs.
+// Element (row, j) is at row * rs + j * cs: (1, k) is R's layout, (n, 1) a row contiguous.
 __global__ __launch_bounds__(1024) void k_winsorize_sort(const double* __restrict__ m, int k, int n, int NP, int ntr,
-                                                         double* __restrict__ out) {
+                                                         long long rs, long long cs, double* __restrict__ out) {
   extern __shared__ double sv[];  // NP values, then NP int indices
   int* si = reinterpret_cast<int*>(sv + NP);
   const int per = (k + 7) / 8;
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(1024) void k_winsorize_sort(const double* __restric
   if (row >= k) return;
   const int tid = threadIdx.x, nt = blockDim.x;
   for (int j = tid; j < NP; j += nt) {
-    sv[j] = j < n ? m[row + (long long)j * k] : INFINITY;
+    sv[j] = j < n ? m[row * rs + j * cs] : INFINITY;
     si[j] = j;
   }
   __syncthreads();
@@ -86,14 +87,14 @@ __global__ __launch_bounds__(1024) void k_winsorize_sort(const double* __restric
     double v = sv[r];
     if (r >= n - ntr) v = maxv;
     else if (r < ntr) v = minv;
-    out[row + (long long)si[r] * k] = v;
+    out[row * rs + si[r] * cs] = v;
   }
 }
 
 // Rows longer than the LDS sort (n > 8192) with ntr <= 32: the ntr + 1 smallest and
 // largest (value, index) pairs by repeated block arg-extremes; everything else unchanged.
 __global__ __launch_bounds__(256) void k_winsorize_select(const double* __restrict__ m, int k, int n, int ntr,
-                                                          double* __restrict__ out) {
+                                                          long long rs, long long cs, double* __restrict__ out) {
   __shared__ double rv[4];
   __shared__ int ri[4];
   __shared__ int lo_idx[33], hi_idx[33];
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void k_winsorize_select(const double* __restri
   const int row = blockIdx.x;
   if (row >= k) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  for (int j = tid; j < n; j += 256) out[row + (long long)j * k] = m[row + (long long)j * k];
+  for (int j = tid; j < n; j += 256) out[row * rs + j * cs] = m[row * rs + j * cs];
   for (int side = 0; side < 2; ++side) {
     for (int t = 0; t <= ntr; ++t) {
       // extreme (value, index) not yet taken: strictly after the previous pick in the order
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(256) void k_winsorize_select(const double* __restri
       double bv = side == 0 ? INFINITY : -INFINITY;
       int bi = side == 0 ? 0x7fffffff : -1;
       for (int j = tid; j < n; j += 256) {
-        const double v = m[row + (long long)j * k];
+        const double v = m[row * rs + j * cs];
         if (side == 0) {
           if (have_prev && !before(pv, pi, v, j)) continue;
           if (before(v, j, bv, bi)) bv = v, bi = j;
@@ -144,10 +145,10 @@ __global__ __launch_bounds__(256) void k_winsorize_select(const double* __restri
   }
   if (tid <= ntr) {
     // ranks < ntr -> minv (sorted[ntr]); ranks >= n - ntr -> maxv (sorted[n - ntr - 1]), the later write winning
-    if (tid < ntr) out[row + (long long)lo_idx[tid] * k] = lo_val[ntr];
+    if (tid < ntr) out[row * rs + lo_idx[tid] * cs] = lo_val[ntr];
   }
   __syncthreads();
-  if (tid < ntr) out[row + (long long)hi_idx[tid] * k] = hi_val[ntr];
+  if (tid < ntr) out[row * rs + hi_idx[tid] * cs] = hi_val[ntr];
 }
 
 // ---- matWCorr: one wave per pair (i < j); three passes over the k rows, the weights
@@ -298,6 +299,40 @@ __global__ void k_pl_diag(int np, double* __restrict__ r, int* __restrict__ cnt)
   cnt[i + (long long)i * np] = 0;
 }
 
+// ---- the random rounds' keep rule, which(abs(sum(diff(abs(x)))) > 0) (R/functions.R:2146), on
+// an ncells x ngenes matrix, one lane per gene: the differences |x[k + 1]| - |x[k]| are rounded to
+// double as R's diff() stores them and summed in cell order in double-double (R's sum()
+// accumulates in long double); the gene is kept iff the sum, rounded to double, is not zero.
+__global__ __launch_bounds__(64) void k_keep_absdiff(const double* __restrict__ x, int ncells, int ngenes,
+                                                     int* __restrict__ keep) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ngenes) return;
+  const double* xg = x + (long long)g * ncells;
+  double hi = 0.0, lo = 0.0;
+  double prev = ncells > 0 ? fabs(xg[0]) : 0.0;
+  for (int k = 1; k < ncells; ++k) {
+    const double cur = fabs(xg[k]);
+    const double d = __dsub_rn(cur, prev);
+    prev = cur;
+    // two-sum of hi + d, the error folded into lo, then renormalised
+    const double s = __dadd_rn(hi, d);
+    const double bb = __dsub_rn(s, hi);
+    const double err = __dadd_rn(__dsub_rn(hi, __dsub_rn(s, bb)), __dsub_rn(d, bb));
+    lo = __dadd_rn(lo, err);
+    hi = __dadd_rn(s, lo);
+    lo = __dsub_rn(lo, __dsub_rn(hi, s));
+  }
+  keep[g] = __dadd_rn(hi, lo) != 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_gather_cols(const double* __restrict__ x, int nrow,
+                                                     const int* __restrict__ cols, long long n,
+                                                     double* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  out[e] = x[(long long)cols[e / nrow] * nrow + e % nrow];
+}
+
 // ------------------------------------------------------------------ launchers
 // ---- pagoda.varnorm: dataset (or batch) modes from a joint posterior, R/functions.R:1426-1430.
 // jp: ngenes x G, element (g, k) at jp[g * jg + k * jk].  mode 1: sum_k jp[g, k] mag[k] in k
@@ -420,7 +455,8 @@ hipError_t launch_vn_matw(const int* counts, long long ld, int ngenes, const int
   return hipGetLastError();
 }
 
-hipError_t launch_winsorize(const double* m, int k, int n, int ntr, double* out, hipStream_t st) {
+static hipError_t winsorize_strided(const double* m, int k, int n, int ntr, long long rs, long long cs, double* out,
+                                    hipStream_t st) {
   int NP = 1;
   while (NP < n) NP <<= 1;
   if (NP <= 8192) {
@@ -430,11 +466,33 @@ hipError_t launch_winsorize(const double* m, int k, int n, int ntr, double* out,
     if (e != hipSuccess) return e;
     const int per = (k + 7) / 8;
     hipLaunchKernelGGL(k_winsorize_sort, dim3(8 * per), dim3(NP >= 1024 ? 1024 : (NP < 64 ? 64 : NP)), lds, st, m,
-                       k, n, NP, ntr, out);
+                       k, n, NP, ntr, rs, cs, out);
     return hipGetLastError();
   }
   if (ntr > 32) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_winsorize_select, dim3(k), dim3(256), 0, st, m, k, n, ntr, out);
+  hipLaunchKernelGGL(k_winsorize_select, dim3(k), dim3(256), 0, st, m, k, n, ntr, rs, cs, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_winsorize(const double* m, int k, int n, int ntr, double* out, hipStream_t st) {
+  return winsorize_strided(m, k, n, ntr, 1, k, out, st);
+}
+
+hipError_t launch_winsorize_gc(const double* x, int ncells, int ngenes, int ntr, double* out, hipStream_t st) {
+  if (ngenes <= 0 || ncells <= 0) return hipSuccess;
+  return winsorize_strided(x, ngenes, ncells, ntr, ncells, 1, out, st);
+}
+
+hipError_t launch_keep_absdiff(const double* x, int ncells, int ngenes, int* keep, hipStream_t st) {
+  if (ngenes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_keep_absdiff, dim3((ngenes + 63) / 64), dim3(64), 0, st, x, ncells, ngenes, keep);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_cols(const double* x, int nrow, const int* cols, int ncols, double* out, hipStream_t st) {
+  const long long n = (long long)nrow * ncols;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, nrow, cols, n, out);
   return hipGetLastError();
 }
 
