@@ -181,13 +181,13 @@ int scde_ctx_reset_kernel_times(scde_ctx* ctx);
  * pair_cells / gene_blocks (pair mode), gene_direct, rest_thread, tables_pair, task_cols,
  * ratio_window / ratio_block: fixed at their defaults.)
  * Statistics: "skip_slabs", "skip_stretches", "skip_kept", "skip_redo", "degen", "tiles_<i>"
- * (k_boot_tiles slabs computing i tiles), "pair_redo" (slabs the gene blocks left to the four-tile
- * list pass) (with skip_stats); "boot_f64_fma" (FP64 lane FMAs the
- * bootstrap kernels issued), also with skip_stats; "boot_path": the bootstrap kernel of the last
- * posterior (0 k_boot2, 1 k_boot_tiles / k_boot_gene, 3 the general k_boot); "stream_syncs",
- * "arena_syncs" (this context's and its peer's streams drained by a buffer regrowth / a pinned
- * arena wrap) and "buf_reallocs" (process-wide workspace reallocations, each a hipFree): 0 in
- * steady state. */
+ * (slabs the tile bootstrap -- gene blocks or list pass -- finished with i 16-point tiles),
+ * "pair_redo" (slabs the gene blocks left to the four-tile list pass) (with skip_stats);
+ * "boot_f64_fma" (FP64 lane FMAs the bootstrap kernels issued), also with skip_stats; "boot_path":
+ * the bootstrap kernel of the last posterior (0 k_boot2, 1 k_boot_tiles / k_boot_gene, 3 the
+ * general k_boot); "stream_syncs", "arena_syncs" (this context's and its peer's streams drained
+ * by a buffer regrowth / a pinned arena wrap) and "buf_reallocs" (process-wide workspace
+ * reallocations, each a hipFree): 0 in steady state. */
 /* Options can also come from the environment: SCDE_OPTIONS="name=value,..." is applied to every
  * context as it is created (an unknown name fails the creation). */
 int scde_ctx_set_option(scde_ctx* ctx, const char* name, double value);

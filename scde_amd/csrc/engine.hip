@@ -272,7 +272,7 @@ struct scde_ctx {
   // fixed-point bootstrap: byte multiplicities, flags/counters
   Buf w8, w8t, w8g, qflags;
   // tile bootstrap gene order: keys, sorted keys, indices, order, sort workspace
-  Buf gkey, gkey2, gidx, gorder, gwork, pmask, pwide, ellw, excd, gdone;
+  Buf gkey, gkey2, gidx, gorder, gwork, pmask, pwide, excd, gdone;
   // options (scde_ctx_set_option; include/scde_hip.h lists them): each a default path's switch or a
   // documented operating / test mode; read from the environment only at creation (SCDE_OPTIONS)
   int opt_boot_skip = 1;         // "boot_skip": grid-stretch / tile skipping in the bootstrap (same bits either way)
@@ -316,14 +316,6 @@ struct scde_ctx {
   std::atomic<long long> st_spins{0};  // handoff spins launched (any thread; the peer counts its own)
   int opt_lanes = 2;            // "lanes": a DE call's two group posteriors run concurrently (2: the second
                                 // group on `peer`, its own streams and workspace) or one after the other (1)
-  // fixed settings that were options until round 5 (the alternatives measured slower or equal and were
-  // removed)
-  static constexpr int opt_ratio_window = 4;   // k_ratio_summary register window
-  static constexpr int opt_ratio_block = 128;  // k_ratio_summary block size
-  static constexpr int opt_upload_threads = 4; // the 16-bit narrowing pool
-  static constexpr int opt_gene_direct = 1;    // gene blocks holding all of a gene's slabs write its jp row
-  static constexpr int opt_ell_chunks = 1;     // the ELL rows in one pass
-  static constexpr int opt_gene_blocks = 1;    // the tile path as k_boot_gene gene blocks
   // the second lane of a DE call: a context on the same device, created on first use; its
   // options are copied from this one per call and its timings/statistics merged back
   scde_ctx* peer = nullptr;
@@ -388,6 +380,7 @@ struct scde_ctx {
     long long free_upto = kRing;  // (under m, as fin and abort)
     int fin[kRing] = {};
     static constexpr int kMaxT = 32;
+    static constexpr int kThreads = 4;  // the narrowing pool's threads (<= kMaxT)
     std::vector<int2> exc[kRing][kMaxT];  // per ring slot and thread: (index in the slot, count)
     std::vector<int2> exc_all;            // one slot's list, uploaded
     bool abort = false;
@@ -416,7 +409,7 @@ struct scde_ctx {
   double st_arena_syncs = 0;   // pinned-arena wraps (this context's streams drained)
   // run_posterior's pieces (host ms): waiting for a piece's upload, then its unique build and tables launch
   double st_piece_wait_ms = 0, st_piece_host_ms = 0;
-  double st_pair_redo = 0;  // slabs a pair pass of k_boot_tiles left to the four-tile list pass
+  double st_pair_redo = 0;  // slabs the gene blocks left to the four-tile list pass (k_boot_tiles)
   double st_boot_path = -1;  // the bootstrap kernel of the last posterior: 0 k_boot2, 1 k_boot_tiles, 3 general
   static constexpr int kQMaxTilesHost = 28;
   double st_tile_hist[kQMaxTilesHost + 1] = {0};
@@ -586,7 +579,7 @@ struct scde_ctx {
                  &ds_x,     &ds_u,       &ds_f,    &ds_p,      &ds_x0,     &ds_cell,   &ds_jpm,   &ds_out,
                  &hc_in,    &hc_ws,      &hc_prob, &hc_out,
                  &gr_raw,   &gr_int,     &gr_prob, &gr_ws,     &gr_out,
-                 &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &ellw,  &excd, &gdone};
+                 &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &excd, &gdone};
     for (Buf* b : wp) b->release();
     for (auto& u : us) u.release();
     for (auto& u : upc) u.release();
@@ -1476,18 +1469,16 @@ int run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std::function<i
     }
     // the baseline columns: T (slow path) or the fused D buffer, which holds T there
     const double* Tbase = fused ? cx->E.as<double>() : cx->T.as<double>();
-    // k_boot_gene (not with pair mode): groups of gene_sg slabs per 4-wave block
-    // k_boot_gene (gene_blocks, the default at every cell count the tile path runs; measured against
-    // pair mode at config 4: bootstrap 11.16 -> 9.94 ms per step) or, without it, k_boot_tiles'
-    // wave per slab (pair mode from pair_cells)
-    const int gene_sg = (tpath && cx->opt_gene_blocks) ? std::min({(s.nboot + nb - 1) / nb, 8, 128 / nb}) : 0;
+    // the tile path's first pass, k_boot_gene: groups of gene_sg slabs per 4-wave block (measured
+    // against the former wave-per-slab pair mode at config 4: bootstrap 11.16 -> 9.94 ms per step)
+    const int gene_sg = tpath ? std::min({(s.nboot + nb - 1) / nb, 8, 128 / nb}) : 0;
     // gene chunks (scde.posteriors, R-layout jp): the bootstrap over genes [gch(k), gch(k + 1))
     // finishes (list pass, fallback, slab sums, exact rows) before chunk k + 1 starts; with jp_host,
     // chunk k's jp rows go back to the host while it runs -- the read-back of the last chunk only is
     // left after the bootstrap.  Calls without the read-back thread (modes_overlap 0, the profiling
     // runs) chunk too, in the descending order below, whose L2 reuse is better (config 4: 29.1 ->
     // 24.1 GB of counter bytes, 10.8 -> 9.85 ms of k_boot_gene per step)
-    const int nchunks = (gene_sg > 0 && s.jp_g == 1 && s.jp_k == N)
+    const int nchunks = (tpath && s.jp_g == 1 && s.jp_k == N)
                             ? std::max(1, std::min(cx->opt_jp_chunks, NBg / 256 + 1)) : 1;
     auto gch = [NBg, nchunks](int k) { return (int)((long long)NBg * k / nchunks); };
     // tile path: genes in order of their count sums (waves in flight share columns in L2), keyed by
@@ -1512,11 +1503,10 @@ int run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std::function<i
       HCHK(cx->gorder.ensure(sizeof(int) * NBg));
     }
     // ELL rows (and the gene-order keys)
-    HCHK(cx->ellw.ensure(std::max<size_t>(1, ell_work_bytes(N, C, cx->opt_ell_chunks))));
     HCHK(launch_ell(u.uci.as<int>(), N, N, C, u.ucl_off.as<long long>(), cx->base_col.as<int>(), stride, (int)ncols,
-                    tpath ? 64 : 8, cx->ent.as<int2>(), cx->nnz.as<int>(), sa, 0, cx->ellw.p,
+                    tpath ? 64 : 8, cx->ent.as<int2>(), cx->nnz.as<int>(), sa, 0,
                     have_order ? u.ucl.as<int>() : nullptr, have_order ? cx->gkey.as<unsigned>() : nullptr,
-                    have_order ? cx->gidx.as<int>() : nullptr, 0, NBg, nchunks, order_desc, cx->opt_ell_chunks));
+                    have_order ? cx->gidx.as<int>() : nullptr, 0, NBg, nchunks, order_desc));
     if (have_order) {
       size_t wb = 0;
       HCHK(launch_gene_order(nullptr, nullptr, NBg, nullptr, nullptr, nullptr, &wb, sa));
@@ -1528,18 +1518,18 @@ int run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std::function<i
       // the multiplicity arrays from the uploaded draw lists, on the device (host loops over
       // sets x cells x boots and their uploads cost ~0.1-0.4 ms of host time per posterior)
       const int P = (s.nboot + nb - 1) / nb;
-      const int NGR = gene_sg > 0 ? (P + gene_sg - 1) / gene_sg : 0;
+      const int NGR = tpath ? (P + gene_sg - 1) / gene_sg : 0;
       const size_t sc = (size_t)nsets * C;
       HCHK(cx->Wt.ensure(sizeof(double) * std::max<size_t>(1, sc * Bp)));
       if (tpath) {
         HCHK(cx->w8.ensure(std::max<size_t>(1, sc * Bt)));
         HCHK(cx->w8t.ensure(std::max<size_t>(1, sc * P * 32)));
-        if (gene_sg > 0) HCHK(cx->w8g.ensure(std::max<size_t>(1, sc * NGR * 128)));
+        HCHK(cx->w8g.ensure(std::max<size_t>(1, sc * NGR * 128)));
       }
       HCHK(launch_mult(cx->draws.as<int>(), nsets, s.nboot, ndraw, C, Bp, cx->Wt.as<double>(), Bt,
                        tpath ? cx->w8.as<unsigned char>() : nullptr, nb, P,
                        tpath ? cx->w8t.as<unsigned char>() : nullptr, gene_sg, NGR,
-                       (tpath && gene_sg > 0) ? cx->w8g.as<unsigned char>() : nullptr, sa));
+                       tpath ? cx->w8g.as<unsigned char>() : nullptr, sa));
     }
     if (tpath && !dev_mult) {
       // byte multiplicities [set][cell][boot] (baseline bound sums and the tile bounds)
@@ -1561,7 +1551,7 @@ int run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std::function<i
         }
       RCHK(upload_on(cx, cx->w8, w8.data(), w8.size(), sa));
       RCHK(upload_on(cx, cx->w8t, w8p.data(), w8p.size(), sa));
-      if (gene_sg > 0) {  // k_boot_gene: per (cell, group of gene_sg slabs) four 32-boot windows as pair slots
+      {  // k_boot_gene: per (cell, group of gene_sg slabs) four 32-boot windows as pair slots
         const int NGR = (P + gene_sg - 1) / gene_sg;
         std::vector<unsigned char> w8g((size_t)nsets * C * NGR * 128, 0);
         for (int set = 0; set < nsets; ++set)
@@ -1690,19 +1680,14 @@ int run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std::function<i
         tb.stats = cx->opt_skip_stats ? cx->qflags.as<int>() + 2 : nullptr;
         HCHK(cx->pmask.ensure(sizeof(unsigned) * std::max<size_t>(1, (size_t)P * NBg)));
         tb.pmask = cx->pmask.as<unsigned>();
-        if (gene_sg > 0) {
-          HCHK(cx->pwide.ensure(sizeof(int) * (1 + (size_t)P * NBg)));
-          tb.wide = cx->pwide.as<int>();
-          tb.gene = 1;
-          tb.SG = gene_sg;
-          tb.kcap = cx->opt_gene_rows;
-          tb.list_cap = cx->opt_gene_list_cap;
-          tb.W8g = cx->w8g.as<unsigned char>();
-          if (cx->opt_gene_direct) {
-            HCHK(cx->gdone.ensure(sizeof(int) * std::max(1, NBg)));
-            tb.gdone = cx->gdone.as<int>();
-          }
-        }
+        HCHK(cx->pwide.ensure(sizeof(int) * (1 + (size_t)P * NBg)));
+        tb.wide = cx->pwide.as<int>();
+        tb.SG = gene_sg;
+        tb.kcap = cx->opt_gene_rows;
+        tb.list_cap = cx->opt_gene_list_cap;
+        tb.W8g = cx->w8g.as<unsigned char>();
+        HCHK(cx->gdone.ensure(sizeof(int) * std::max(1, NBg)));
+        tb.gdone = cx->gdone.as<int>();
         if (have_order) tb.order = cx->gorder.as<int>();
         if (nchunks > 1) {
           for (int k = 0; k < nchunks; ++k) {
@@ -2417,8 +2402,6 @@ static int ratio_common(const double* pmat1, const double* pmat2, int nrows, int
   ra.res = res ? cx->res.as<double>() : nullptr;
   ra.res_ld = nrows;
   hipEvent_t ev = cx->mark_begin(SLOT_RATIO);
-  ra.window = cx->opt_ratio_window;
-  ra.block = cx->opt_ratio_block;
   HCHK(launch_ratio_summary(ra, st));
   cx->mark_end(SLOT_RATIO, ev);
   if (ratio && nrows) HCHK(hipMemcpyAsync(ratio, ra.ratio, sizeof(double) * nrows * m, hipMemcpyDeviceToHost, st));
@@ -2448,8 +2431,6 @@ int scde_distribution_summary(const double* rpost, int nrows, int m, const doubl
   ra.zi = zi;
   ra.res = cx->res.as<double>();
   ra.res_ld = nrows;
-  ra.window = cx->opt_ratio_window;
-  ra.block = cx->opt_ratio_block;
   HCHK(launch_ratio_summary(ra, st));
   if (nrows) HCHK(hipMemcpyAsync(res, ra.res, sizeof(double) * nrows * 5, hipMemcpyDeviceToHost, st));
   return cx->sync();
@@ -2556,7 +2537,8 @@ static int upload_cols_u16(scde_ctx* ctx, const HostUpload& h, int lo, int hi) {
     HCHK(hipMalloc(reinterpret_cast<void**>(&r.dev), sizeof(unsigned short) * R::kRing * R::kSlotCounts));
     for (auto& e : r.ev) HCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
   }
-  const int T = std::max(1, std::min(R::kMaxT, ctx->opt_upload_threads));
+  static_assert(R::kThreads >= 1 && R::kThreads <= R::kMaxT, "the pool's per-thread lists");
+  const int T = R::kThreads;
   if ((int)r.th.size() != T) {  // (re)build the pool (no job is running: the upload worker is its only user)
     if (!r.th.empty()) {
       {
@@ -3190,8 +3172,6 @@ static int de_run(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, 
   ra.res = ctx->res.as<double>();
   ra.res_ld = ngenes;
   hipEvent_t ev = ctx->mark_begin(SLOT_RATIO);
-  ra.window = ctx->opt_ratio_window;
-  ra.block = ctx->opt_ratio_block;
   HCHK(launch_ratio_summary(ra, st));
   ctx->mark_end(SLOT_RATIO, ev);
   if (p->compute_cz && ngenes) {
@@ -3380,8 +3360,6 @@ int scde_expression_difference_batch_dev(scde_ctx* ctx, const int* counts_dev, i
     ra.res = rres;
     ra.res_ld = N;
     hipEvent_t ev = ctx->mark_begin(SLOT_RATIO);
-    ra.window = ctx->opt_ratio_window;
-    ra.block = ctx->opt_ratio_block;
     HCHK(launch_ratio_summary(ra, st));
     ctx->mark_end(SLOT_RATIO, ev);
     if (N) HCHK(launch_bh_cz(rres + (size_t)4 * N, N, rres + (size_t)5 * N, ctx->bhw.p, &wb, st));

@@ -159,8 +159,10 @@ struct Boot2Args {
   double slack;  // heuristic slack of the mask (NaN: the default 20 + 0.15 C)
 };
 
-// k_boot_tiles (with Boot2Args; needs G <= 448): multiplicities as bytes and the tables'
-// 16-point tile bounds for the exact integer tile bounds of each (gene, slab)
+// The tile bootstrap (with Boot2Args; needs G <= 448): multiplicities as bytes and the tables'
+// 16-point tile bounds for the exact integer tile bounds of each (gene, slab).  k_boot_gene: a
+// 4-wave block per (gene, group of SG slabs), 16 rows shared by the group's slabs; the slabs it
+// cannot finish take k_boot_tiles, the four-tile list pass over `wide`, and its failures k_boot2.
 struct TileBootArgs {
   const unsigned char* W8p;  // [nsets][ncells][P][32] draw multiplicities (<= 127): per slab the pairs
                              // (boot r, boot 16 + r) of its boots, r < 16 (0 past the slab's live boots)
@@ -171,18 +173,17 @@ struct TileBootArgs {
   int maxgroups;             // 32-point bound tiles computed per slab, 1..4 (4; tests force the fallback with fewer)
   int* stats;                // nullable: [0] slabs, [1] tiles computed, [2] tiles, [3] slabs left to k_boot2,
                              // [4] sum of groups x entries (FMA count / (64 nb)), [5] entries of the slabs left,
-                             // [6 + i] slabs that computed i tiles (i <= 28), [35] slabs a pair pass left
+                             // [6 + i] slabs that computed i tiles (i <= 28), [35] slabs the gene blocks
+                             // left to the list pass
   const int* order;          // nullable: genes in this order (launch_gene_order)
   unsigned* pmask;           // [ngenes][P] tiles each slab's partial row holds (k_sum_partials reads those)
-  int* wide = nullptr;       // [1 + ngenes * P] the list pass's slabs: [0] length, then g * P + p
-  int gene = 0;              // k_boot_gene: a 4-wave block per (gene, group of SG slabs), 16 rows shared
-                             // by the group's slabs; failures take the list pass over `wide`
-  int SG = 0;                // slabs per group (<= 8, SG x nb <= 128)
+  int* wide = nullptr;       // required: [1 + ngenes * P] the list pass's slabs: [0] length, then g * P + p
+  int SG = 0;                // required: slabs per group (1..8, SG x nb <= 128)
   int kcap = 4;              // rows per slab at most (tests force the list pass with fewer)
   int list_cap = 0;          // slabs the list pass takes at most (0: 16384; tests force the overflow to k_boot2)
-  const unsigned char* W8g = nullptr;  // [nsets][ncells][groups][4 windows][32] the group's boots 32 w + j
-                                       // as pair slots (boot 32 w + j, 32 w + 16 + j), 0 past its boots
-  // gene blocks only: this launch takes genes [g_lo, g_hi) (g_hi < 0: all) -- a posterior's bootstrap in
+  const unsigned char* W8g = nullptr;  // required: [nsets][ncells][groups][4 windows][32] the group's boots
+                                       // 32 w + j as pair slots (boot 32 w + j, 32 w + 16 + j), 0 past its boots
+  // this launch takes genes [g_lo, g_hi) (g_hi < 0: all) -- a posterior's bootstrap in
   // gene chunks, each finished (list pass, fallback, slab sums) before the next, so its jp rows can
   // be read back while the next chunk runs; `order` then holds each chunk's genes sorted within it
   int g_lo = 0, g_hi = -1;
@@ -244,7 +245,6 @@ struct RatioArgs {
   int zi;
   double* res;  // nullable; column-major res_ld x 5 (lb, mle, ub, ce, Z)
   long long res_ld;
-  int window, block;  // register-window width R (4, 5, 7, 8) and block size (64/128/256); 0 = default
 };
 
 hipError_t launch_cell_prep(const double* models, int ncells, int G, int GS, const double* mag, int lt, int sq,
@@ -259,24 +259,21 @@ hipError_t launch_stretch_zu(const double* U, const int* base_col, int ncells, c
                              double* ZU, hipStream_t s, int gsets = 0, int gsplit = 0);
 hipError_t launch_base_cols(const int* ucl, const long long* ucl_off, int ncells, const unsigned char* has_clamp,
                             int use_baseline, int* base_col, hipStream_t s);
-// padto 8: rows padded to a multiple of 8 plus one batch of 8 (k_boot2's look-ahead); 64: to a
-// multiple of 64 plus 8 (k_boot_tiles' bound MFMAs take 64-entry steps)
-// cell_off: added to the cell of every entry (a fused second group's cells follow the first's)
-// work: ell_work_bytes(ngenes, ncells) bytes (null allowed when that is 0) -- the per cell-chunk
-// entry counts and count sums of the two-pass build.  key (nullable, with ucl and idx): the
-// tile bootstrap's 16-bit gene-order keys (log-scaled sums of the entries' counts ucl[col]) and gene indices, the
-// launch's genes being genes kg0 .. of kgn split into kch gene chunks (the chunk index in the
-// key's top bits; desc: descending within a chunk)
 // out[i] = in[i] for n 16-bit counts
 hipError_t launch_widen16(const unsigned short* in, int* out, size_t n, hipStream_t s);
 // out[exc[i].x] = exc[i].y for n listed counts (indices relative to out)
 hipError_t launch_patch32(const int2* exc, size_t n, int* out, hipStream_t s);
-// max_chunks: at most this many cell chunks (0: as many as fill the chip twice, at most 64)
-size_t ell_work_bytes(int ngenes, int ncells, int max_chunks = 0);
+// padto 8: rows padded to a multiple of 8 plus one batch of 8 (k_boot2's look-ahead); 64: to a
+// multiple of 64 plus 8 (the tile bootstrap's bound MFMAs take 64-entry steps)
+// cell_off: added to the cell of every entry (a fused second group's cells follow the first's)
+// key (nullable, with ucl and idx): the tile bootstrap's 16-bit gene-order keys (log-scaled sums
+// of the entries' counts ucl[col]) and gene indices, the launch's genes being genes kg0 .. of kgn
+// split into kch gene chunks (the chunk index in the key's top bits; desc: descending within a
+// chunk)
 hipError_t launch_ell(const int* uci, long long ld_uci, int ngenes, int ncells, const long long* ucl_off,
                       const int* base_col, int stride, int pad_col, int padto, int2* ent, int* nnz, hipStream_t s,
-                      int cell_off, void* work, const int* ucl = nullptr, unsigned* key = nullptr, int* idx = nullptr,
-                      int kg0 = 0, int kgn = 0, int kch = 1, int desc = 0, int max_chunks = 0);
+                      int cell_off, const int* ucl = nullptr, unsigned* key = nullptr, int* idx = nullptr,
+                      int kg0 = 0, int kgn = 0, int kch = 1, int desc = 0);
 hipError_t launch_baseline_z(const double* T, int G, int GS, const int* base_col, int ncells, const double* Wt,
                              int Bp, int nsets, double* Z, hipStream_t s, int gsets = 0, int gsplit = 0);
 // Draw multiplicities on the device from the draw lists draws[nsets][nboot][ndraw] (cell index, -1

@@ -1316,19 +1316,17 @@ __global__ void k_base_cols(const int* __restrict__ ucl, const long long* __rest
 // ELL rows: per gene the (cell, column) pairs of the cells whose column is not the cell's
 // baseline, in cell order, then pad entries (cell 0, the zero column) to a multiple of 8 plus
 // one look-ahead batch of 8 (k_boot2), or with padto 64 to whole 64-entry steps plus 8 (the tile
-// bootstrap's bounds).  A block takes 64 genes x one chunk of `ccells` cells: each 64-cell step
-// of uci (genes fastest, as R lays out the count matrix) is read coalesced into an LDS tile
-// (stride 65 against bank conflicts), then each wave compacts its 4 genes' entries with ballots
-// (mbcnt prefix, cell order kept).  With nchk > 1 cell chunks a first pass (WRITE = false)
-// counts each (gene, chunk)'s entries and rank sum, and the second writes each chunk's entries
-// after the earlier chunks' (a grid of ngenes / 64 blocks alone left most CUs idle: config 4's
-// 30k x 2000 took 330-420 us in one pass over 32 serial cell steps per block).  The last chunk's
-// block writes the row length, the pad entries and, with `key`, the gene's 16-bit tile-order
-// key: the sum of its entries' counts (ucl[col]) on a log scale -- genes of like expression next
-// to each other, so that waves in flight share columns -- under its gene chunk's index in the
-// top bits (kch chunks of the kgn genes, this launch's genes from kg0), descending when `desc`
-// (heaviest genes first within each chunk).  (Timing build SCDE_ELL_KEY_RANK: the sum of the count ranks,
-// uci, instead, no gather: the same bootstrap fetch, 28.5-28.6 GB per launch at config 4.)
+// bootstrap's bounds).  A block takes 64 genes and every cell: each 64-cell step of uci (genes
+// fastest, as R lays out the count matrix) is read coalesced into an LDS tile (stride 65
+// against bank conflicts), then each wave compacts its genes' entries with ballots (mbcnt
+// prefix, cell order kept).  (A two-pass build over cell chunks, which fills the CUs a grid of
+// ngenes / 64 blocks leaves idle, was measured and lost.)  The block then writes the row
+// length, the pad entries and, with `key`, the gene's 16-bit tile-order key: the sum of its
+// entries' counts (ucl[col]) on a log scale -- genes of like expression next to each other, so
+// that waves in flight share columns -- under its gene chunk's index in the top bits (kch chunks
+// of the kgn genes, this launch's genes from kg0), descending when `desc` (heaviest genes first
+// within each chunk).  (Timing build SCDE_ELL_KEY_RANK: the sum of the count ranks, uci,
+// instead, no gather: the same bootstrap fetch, 28.5-28.6 GB per launch at config 4.)
 #ifndef SCDE_ELL_KEY_RANK
 #define SCDE_ELL_KEY_RANK 0
 #endif
@@ -1340,21 +1338,18 @@ __global__ void k_base_cols(const int* __restrict__ ucl, const long long* __rest
 #define SCDE_ELL_WAVES 8
 #endif
 constexpr int kEllWaves = SCDE_ELL_WAVES;
-constexpr int kEllMaxChunks = 64;
 constexpr int kEllKeyBits = 16;  // gene-order key width (launch_gene_order sorts these bits)
-template <bool WRITE>
 __global__ __launch_bounds__(64 * kEllWaves) void k_ell(const int* __restrict__ uci, long long ld_uci, int ngenes,
                                              int ncells, const long long* __restrict__ ucl_off,
                                              const int* __restrict__ base_col, int stride, int pad_col,
                                              int padto, int2* __restrict__ ent, int* __restrict__ nnz, int cell_off,
-                                             int ccells, int nchk, unsigned* __restrict__ cnt,
-                                             unsigned* __restrict__ ksum, const int* __restrict__ ucl,
-                                             unsigned* __restrict__ key, int* __restrict__ idx, int kg0, int kgn,
-                                             int kch, int desc) {
+                                             const int* __restrict__ ucl, unsigned* __restrict__ key,
+                                             int* __restrict__ idx, int kg0, int kgn, int kch, int desc) {
   __shared__ int tile[64][65];  // [cell][gene]
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int g0 = blockIdx.x * 64, cy = blockIdx.y;
-  const int cbeg = cy * ccells, cend = min(ncells, cbeg + ccells);
+  // wid through readfirstlane: the wave's genes, rows and entry counts are then scalar values,
+  // which keeps the kernel at 6 or more waves per SIMD (as a vector value wid cost 95 VGPRs)
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g0 = blockIdx.x * 64;
   constexpr int GPW = 64 / kEllWaves;  // genes per wave
   const bool want_key = key != nullptr;
   int n[GPW];
@@ -1363,11 +1358,6 @@ __global__ __launch_bounds__(64 * kEllWaves) void k_ell(const int* __restrict__ 
   for (int i = 0; i < GPW; ++i) {
     n[i] = 0;
     ks[i] = 0;
-    if (WRITE && cy > 0) {  // the earlier chunks' entries come first
-      const int g = g0 + wid * GPW + i;
-      if (g < ngenes)
-        for (int k = 0; k < cy; ++k) n[i] += (int)cnt[(long long)k * ngenes + g];
-    }
   }
   // software pipeline: the next 64-cell step's uci rows (this wave's 4 rows of the tile) and
   // its lane cell's column offset and baseline column are loaded before the current step is
@@ -1380,25 +1370,25 @@ __global__ __launch_bounds__(64 * kEllWaves) void k_ell(const int* __restrict__ 
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       const int c = c0 + wid + r * kEllWaves, g = g0 + lane;
-      pu[r] = (c < cend && g < ngenes) ? uci[(long long)g + ld_uci * c] : 0;
+      pu[r] = (c < ncells && g < ngenes) ? uci[(long long)g + ld_uci * c] : 0;
     }
     const int c = c0 + lane;
     poff = 0;
     pbc = -1;
-    if (c < cend) {
+    if (c < ncells) {
       poff = ucl_off[c];
       pbc = base_col[c];
     }
   };
-  if (cbeg < cend) prefetch(cbeg);
-  for (int c0 = cbeg; c0 < cend; c0 += 64) {
+  if (ncells > 0) prefetch(0);
+  for (int c0 = 0; c0 < ncells; c0 += 64) {
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < RPW; ++r) tile[wid + r * kEllWaves][lane] = pu[r];
     const long long off = poff;
     const int bc = pbc;
     __syncthreads();
-    if (c0 + 64 < cend) prefetch(c0 + 64);
+    if (c0 + 64 < ncells) prefetch(c0 + 64);
     const int c = c0 + lane;
 #pragma unroll
     for (int i = 0; i < GPW; ++i) {
@@ -1407,16 +1397,14 @@ __global__ __launch_bounds__(64 * kEllWaves) void k_ell(const int* __restrict__ 
       int col = -1;
       bool keep = false;
       int rank = 0;
-      if (c < cend) {
+      if (c < ncells) {
         rank = tile[lane][gl];
         col = (int)(off + rank);
         keep = col != bc;
       }
       const unsigned long long m = __ballot(keep);
-      if (WRITE) {
-        const int pos = n[i] + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (keep) ent[(long long)g * stride + pos] = make_int2(c + cell_off, col);
-      }
+      const int pos = n[i] + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+      if (keep) ent[(long long)g * stride + pos] = make_int2(c + cell_off, col);
       if (want_key && keep) ks[i] += (unsigned)max(SCDE_ELL_KEY_RANK ? rank : ucl[col], 0);
       n[i] += __popcll(m);
     }
@@ -1430,19 +1418,10 @@ __global__ __launch_bounds__(64 * kEllWaves) void k_ell(const int* __restrict__ 
 #pragma unroll
       for (int o = 32; o >= 1; o >>= 1) kv += __shfl_xor(kv, o, 64);
     }
-    if (!WRITE) {  // this chunk's entries (n counts only this chunk here) and count sum
-      if (lane == 0) {
-        cnt[(long long)cy * ngenes + g] = (unsigned)n[i];
-        if (want_key) ksum[(long long)cy * ngenes + g] = kv > 0xffffffffull ? 0xffffffffu : (unsigned)kv;
-      }
-      continue;
-    }
-    if (cy != nchk - 1) continue;
     const int nn = n[i];
     if (lane == 0) {
       nnz[g] = nn;
       if (want_key) {
-        for (int k = 0; k < cy; ++k) kv += ksum[(long long)k * ngenes + g];
         // the gene chunk of gene kg0 + g: chunk k holds [kgn k / kch, kgn (k + 1) / kch)
         const long long gg = (long long)kg0 + g;
         int k = (int)(gg * kch / kgn);
@@ -2426,8 +2405,11 @@ __global__ __launch_bounds__(32 * kQTiles) void k_zuq(const unsigned* __restrict
 }
 
 // ------------------------------------------------------------------ tile bootstrap
-// k_boot_tiles: k_boot2's FP64 bootstrap computed only where it matters.  One wave per
-// (gene, slab of NB boots), four per block; the waves never synchronise with each other.
+// The tile bootstrap: k_boot2's FP64 bootstrap computed only where it matters.  k_boot_gene
+// (below) takes every (gene, slab of NB boots) first, sharing a block's 16 rows among a gene's
+// slabs; k_boot_tiles is the list pass behind it, over the slabs whose post-check failed there
+// (the list k_boot_gene leaves in `wide`), with a fixed four bound tiles each.  One wave per
+// listed slab, four per block; the waves never synchronise with each other.
 //   1. bounds UB_bt = ZU_bt + sum_e W_be UQ_et for every boot and 32-point bound tile t (UQ:
 //      the tables' per-tile column maxima in units of 2^-8, rounded up; ZU: the baseline
 //      cells' part), exact integers on the int8 matrix cores (4 balanced digits), kept in LDS
@@ -2447,7 +2429,7 @@ __global__ __launch_bounds__(32 * kQTiles) void k_zuq(const unsigned* __restrict
 constexpr int kTileMax = 28;   // 16-point sum tiles, G <= 448
 constexpr int kBTileMax = 14;  // 32-point bound tiles, G <= 448
 #ifndef SCDE_TILE_DIAG
-#define SCDE_TILE_DIAG 0  // timing builds: 1 = bounds only, 2 = rows without bounds, 4 = no multiplicity loads,
+#define SCDE_TILE_DIAG 0  // timing builds: 4 = no multiplicity loads,
                           // 8 = every column load from the entry-0 column (cache-resident); k_boot_gene:
                           // 16 = bounds replaced by -inf, 512 = no bound pass, 32 = no row loop, 64 = rows only (no
                           // softmax / sums / rows out), 128 = bound pass loads only, 256 = bound pass without MFMA;
@@ -2787,56 +2769,42 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
     int G, int GS, int P, int nboot, double norm_mult, double degen_thresh, double* __restrict__ part,
     long long part_stride, int* __restrict__ degen, int ngenes, const unsigned char* __restrict__ W8p, int Bq,
     const unsigned* __restrict__ UQ, const int* __restrict__ ZUq, const int* __restrict__ nanflag, int maxgroups,
-    int* __restrict__ redo, int* __restrict__ stats, const int* __restrict__ order, unsigned* __restrict__ pmask,
-    const int* __restrict__ ilist) {
+    int* __restrict__ redo, int* __restrict__ stats, unsigned* __restrict__ pmask,
+    const int* __restrict__ slab_list) {
   static_assert(NB % 4 == 0 && NB <= 20, "NB must be a multiple of 4, <= 20");
-  __shared__ float ubs[WB][kBTileMax * NB];  // [wave][bound tile][boot] slab A's bounds
+  __shared__ float ubs[WB][kBTileMax * NB];  // [wave][bound tile][boot] the slab's bounds
 #ifdef SCDE_TILE_TEST_WB1
   __shared__ unsigned bstage[WB][64];  // hazard-test builds: the LDS that would cap occupancy (never run)
 #else
   __shared__ unsigned bstage[WB][1024 + 512];  // [wave] bound staging: 16 x 64 tile words | 16 x 32 pair words
 #endif
-  __shared__ float fmx[WB][2][32];          // [wave][slab][boot] maxima
+  __shared__ float fmx[WB][32];  // [wave][boot] maxima
   __shared__ double etab[64];
   const int lane = threadIdx.x & 63;
   const int wsid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // list mode: blocks past the list's end leave before the block barrier (the list pass is
-  // launched for the longest list the first pass may build; most of its blocks find no item)
-  if (ilist && xcd_block(blockIdx.x, gridDim.x) * WB >= ilist[0]) return;
+  // slab_list: [0] the number of items, [1 + i] item i = gene * P + slab.  Blocks past the list's
+  // end leave before the block barrier (the pass is launched for the longest list the gene
+  // blocks may build; most of its blocks find no item)
+  if (xcd_block(blockIdx.x, gridDim.x) * WB >= slab_list[0]) return;
   if (threadIdx.x < 64) etab[threadIdx.x] = kExp2Frac64[threadIdx.x];
   __syncthreads();
-  // the bound staging area, once the bound loops are done: slab B's bounds | tile partial sums
-  // [slot][boot] | 1 / (S nboot) [slab][boot] (the shipped 4-wave block stays under 40 KB of LDS:
-  // four blocks, 16 waves per CU)
+  // the bound staging area, once the bound loop is done: tile partial sums [slot][boot] |
+  // 1 / (S nboot) [boot] (the shipped 4-wave block stays under 40 KB of LDS: four blocks, 16
+  // waves per CU)
 #ifndef SCDE_TILE_TEST_WB1
-  static_assert(2 * ((kBTileMax * NB + 1) / 2) + 2 * (8 * NB + 2 * 32) <= (int)(sizeof(bstage[0]) / 4),
-                "the staging area must hold slab B's bounds, the tile sums and the normalisers");
+  static_assert(2 * (8 * NB + NB) <= (int)(sizeof(bstage[0]) / 4),
+                "the staging area must hold the tile sums and the normalisers");
 #endif
-  float* const ubB = reinterpret_cast<float*>(&bstage[wsid][0]);
-  double* const tsum = reinterpret_cast<double*>(&bstage[wsid][2 * ((kBTileMax * NB + 1) / 2)]);
+  double* const tsum = reinterpret_cast<double*>(&bstage[wsid][0]);
   double* const finv = tsum + 8 * NB;
-  // ---- the wave's slab: (gene, slab) items; in list mode the slabs the gene blocks could not
-  // finish, all four bound tiles each.  (Slab B -- pB, nsl, pr -- is the former pair mode's second
-  // slab of a wave, never set since round 6: the branches below fold away.)
+  // ---- the wave's item: one slab a gene block could not finish
   const int idx = xcd_block(blockIdx.x, gridDim.x) * WB + wsid;
-  int g, pA;
-  constexpr int pB = -1;
-  if (ilist) {
-    if (idx >= ilist[0]) return;
-    const int it = ilist[1 + idx];
-    g = it / P;
-    pA = it - g * P;
-  } else {
-    if (idx >= ngenes * P) return;
-    const int gi = idx / P;
-    g = order ? order[gi] : gi;
-    pA = idx - gi * P;
-  }
-  constexpr bool pr = false;
-  constexpr int nsl = 1;
+  if (idx >= slab_list[0]) return;
+  const int it = slab_list[1 + idx];
+  const int g = it / P, p = it - g * P;
   if (*nanflag) {  // a NaN in some table: k_boot2 computes every slab
-    if (lane < nsl) {
-      const int q = (long long)g * P + (lane ? pB : pA);
+    if (lane == 0) {
+      const int q = (long long)g * P + p;
       redo[q] = 1;
       redo[(long long)ngenes * P + 1 + atomicAdd(&redo[(long long)ngenes * P], 1)] = q;
       pmask[q] = ~0u;
@@ -2848,144 +2816,101 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
   const int r = lane & 15;
   const int2* __restrict__ E = ent + (long long)g * ent_stride;
   const int set = wset ? wset[g] : 0;
+  const int b0 = p * NB;
   // ---- 1. bound tiles (C layout of the 16x16x64 MFMA: bound tile r, boots 16 bt + 4 h + q).  Per
   // 64-entry chunk each lane loads one entry's data with wide loads -- its (cell, column), the
   // column's 16 tile bounds (64 B) and the cell's 16 multiplicity pairs of this slab (32 B) --
   // and writes them transposed into the wave's LDS area; the MFMA fragments are then contiguous
   // LDS reads: 7 vector-memory instructions per chunk instead of 40 single-entry gathers.
-#pragma unroll 1
-  for (int sl = 0; sl < nsl; ++sl) {
-    const int p = sl ? pB : pA, b0 = p * NB;
-    float* ub = sl ? ubB : ubs[wsid];
-    if (SCDE_TILE_DIAG & 2) {  // timing build: rows without bounds (results wrong)
-      for (int i = lane; i < kBTileMax * NB; i += 64) ub[i] = 0.0f;
-      continue;
-    }
+  {
     const unsigned pstride = 32u * (unsigned)P;
     const unsigned char* __restrict__ W8 = W8p + (long long)set * ncells * pstride + 32 * p;
     const int* __restrict__ ZU = ZUq + (long long)set * 4 * kQTiles * Bq + b0;
-    tile_bound_pass(E, n, UQ, W8, pstride, ZU, Bq, &bstage[wsid][0], ub, NB, NB, NTB, lane);
+    tile_bound_pass(E, n, UQ, W8, pstride, ZU, Bq, &bstage[wsid][0], ubs[wsid], NB, NB, NTB, lane);
   }
-#if SCDE_TILE_DIAG & 1
-  return;  // timing build: bounds only
-#endif
   wave_sync();
-  const int b0A = pA * NB, b0B = pr ? pB * NB : 0;
-  const int nliveA = min(NB, nboot - b0A), nliveB = pr ? min(NB, nboot - b0B) : 0;
-  // ---- 2. per slab the bound tiles with the largest bound over its live boots: four (one
-  // slab; maxgroups, the tests force the fallback with fewer), two each (a pair); all of them
-  // when the grid has no more
-  float scA = -INFINITY, scB = -INFINITY;
-  if (lane < NTB) {
-    for (int b = 0; b < nliveA; ++b) scA = fmaxf(scA, ubs[wsid][lane * NB + b]);
-    for (int b = 0; b < nliveB; ++b) scB = fmaxf(scB, ubB[lane * NB + b]);
-  }
-  const int nsel = pr ? min(2, NTB) : min(max(1, min(maxgroups, 4)), NTB);  // tiles per slab
+  const int nlive = min(NB, nboot - b0);
+  // ---- 2. the four bound tiles with the largest bound over the slab's live boots (maxgroups:
+  // the tests force the fallback with fewer); all of them when the grid has no more
+  float sc = -INFINITY;
+  if (lane < NTB)
+    for (int b = 0; b < nlive; ++b) sc = fmaxf(sc, ubs[wsid][lane * NB + b]);
+  const int nsel = min(max(1, min(maxgroups, 4)), NTB);
   int tl[4] = {0, 0, 0, 0};
-  unsigned bdA = 0, bdB = 0;  // bound tiles computed, per slab
+  unsigned bd = 0;  // bound tiles computed
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const bool onB = pr && j >= 2;
-    if ((pr ? (j & 1) : j) < nsel) {
+    if (j < nsel) {
       // the 16 bound-tile scores sit in lanes 0..15: a 16-lane DPP max, read back from lane 0
-      const float sc = onB ? scB : scA;
       float m = sc;
       m = fmaxf(m, dpp_f<kDppXor1>(m));
       m = fmaxf(m, dpp_f<kDppXor2>(m));
       m = fmaxf(m, dpp_f<kDppHalfMirror>(m));
       m = fmaxf(m, dpp_f<kDppMirror>(m));
       m = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m)));
-      const unsigned bd = onB ? bdB : bdA;
       const unsigned long long bl = __ballot(lane < NTB && !((bd >> lane) & 1) && sc == m);
       const int t = __ffsll((long long)bl) - 1;
       tl[j] = t;
-      if (onB) {
-        bdB |= 1u << t;
-        if (lane == t) scB = -INFINITY;
-      } else {
-        bdA |= 1u << t;
-        if (lane == t) scA = -INFINITY;
-      }
+      bd |= 1u << t;
+      if (lane == t) sc = -INFINITY;
     }
   }
-  // the 16-point sum tiles of the computed bound tiles, per slab
+  // the 16-point sum tiles of the computed bound tiles
   const unsigned ntmask = (NT >= 32) ? ~0u : ((1u << NT) - 1);
-  unsigned doneA = 0, doneB = 0;
+  unsigned done = 0;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if ((pr ? (j & 1) : j) >= nsel) continue;
-    if (pr && j >= 2)
-      doneB |= 3u << (2 * tl[j]);
-    else
-      doneA |= 3u << (2 * tl[j]);
-  }
-  doneA &= ntmask;
-  doneB &= ntmask;
-  // lane l: row l >> 4 = one bound tile of one slab; sum tile slot l >> 3 (its half l >> 3 & 1)
+  for (int j = 0; j < 4; ++j)
+    if (j < nsel) done |= 3u << (2 * tl[j]);
+  done &= ntmask;
+  // lane l: row l >> 4 = one bound tile; sum tile slot l >> 3 (its half l >> 3 & 1)
   const int slot = lane >> 3, m2 = lane & 7, row = lane >> 4;
   int mybt = tl[0];
 #pragma unroll
   for (int j = 1; j < 4; ++j) mybt = (row == j) ? tl[j] : mybt;
-  const int mys = (pr && row >= 2) ? 1 : 0;  // the lane's slab
   const int mytile = 2 * mybt + (slot & 1);
   const int k0 = 16 * mytile + 2 * m2;
-  const bool live = (pr ? (row & 1) : row) < nsel;
+  const bool live = row < nsel;
   const bool l0 = live && k0 < G, l1 = live && k0 + 1 < G;
-  const int b0 = mys ? b0B : b0A;
   const double* __restrict__ W = Wt + (long long)set * ncells * Bp;
   const double* __restrict__ Zs = Z + (long long)set * Bp * GS;
   // ---- rows: Z_b + sum_e W_be D_e at points k0, k0 + 1 (k0 even: 16-byte aligned pairs)
   double a0[NB], a1[NB];
   tile_rows<NB>(a0, a1, D, E, n, W, Zs, GS, Bp, b0, k0, r, live, l0, l1);
-  // per slab maxima m'_b (f32) over its lanes -> fmx[wsid][slab]
-#pragma unroll 1
-  for (int sl = 0; sl < nsl; ++sl) {
+  // the slab's maxima m'_b (f32) over the wave's lanes -> fmx[wsid]
+  {
     double mx[NB];
 #pragma unroll
-    for (int i = 0; i < NB; ++i) mx[i] = (mys == sl) ? gt_max(a0[i], a1[i]) : -INFINITY;
-    wave_max_partials_all<NB>(mx, &fmx[0][0][0], lane, 2 * wsid + sl);
+    for (int i = 0; i < NB; ++i) mx[i] = gt_max(a0[i], a1[i]);
+    wave_max_partials_all<NB>(mx, &fmx[0][0], lane, wsid);
   }
   wave_sync();
-  // ---- 3. post-check per slab: every bound tile not computed stays below the exact maxima
-  // minus 51; a slab that fails goes whole to the four-tile list pass (pair mode) or to
-  // k_boot2's fallback launch
-  unsigned failm = 0;
-#pragma unroll 1
-  for (int sl = 0; sl < nsl; ++sl) {
-    const unsigned bd = sl ? bdB : bdA;
-    const int nl = sl ? nliveB : nliveA;
-    bool need = false;
-    if (lane < NTB && !((bd >> lane) & 1))
-      for (int b = 0; b < nl; ++b) need |= (double)(sl ? ubB : ubs[wsid])[lane * NB + b] >= (double)fmx[wsid][sl][b] - 51.0;
-    if (SCDE_TILE_DIAG & 2) need = false;
-    if (__ballot(need)) {
-      failm |= 1u << sl;
-      if (lane == 0) {
-        const int q = g * P + (sl ? pB : pA);
-        redo[q] = 1;
-        redo[(long long)ngenes * P + 1 + atomicAdd(&redo[(long long)ngenes * P], 1)] = q;
-        pmask[q] = ~0u;
-        if (stats) {
-          atomicAdd(&stats[3], 1);
-          atomicAdd(&stats[5], (n + 3) & ~3);
-        }
-      }
+  // ---- 3. post-check: every bound tile not computed stays below the exact maxima minus 51; a
+  // slab that fails goes whole to k_boot2's fallback launch
+  bool need = false;
+  if (lane < NTB && !((bd >> lane) & 1))
+    for (int b = 0; b < nlive; ++b) need |= (double)ubs[wsid][lane * NB + b] >= (double)fmx[wsid][b] - 51.0;
+  const bool fail = __ballot(need) != 0;
+  if (fail && lane == 0) {
+    const int q = g * P + p;
+    redo[q] = 1;
+    redo[(long long)ngenes * P + 1 + atomicAdd(&redo[(long long)ngenes * P], 1)] = q;
+    pmask[q] = ~0u;
+    if (stats) {
+      atomicAdd(&stats[3], 1);
+      atomicAdd(&stats[5], (n + 3) & ~3);
     }
   }
   if (stats && lane == 0) atomicAdd(&stats[4], 2 * ((n + 1) & ~1));  // 128 points = two 64-lane groups' FMAs
-  if (failm == (pr ? 3u : 1u)) return;
-  const bool mine = !((failm >> mys) & 1);  // the lane's slab is finished here
-  if (lane < nsl && !((failm >> lane) & 1)) {
-    const int nl = lane ? nliveB : nliveA;
-    for (int b = 0; b < nl; ++b)
-      if (!(fabs((double)fmx[wsid][lane][b]) <= degen_thresh)) degen[g] = 1;
-  }
+  if (fail) return;
+  if (lane == 0)
+    for (int b = 0; b < nlive; ++b)
+      if (!(fabs((double)fmx[wsid][b]) <= degen_thresh)) degen[g] = 1;
   // ---- 4. softmax terms, tile partial sums, jp partial rows
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
-    const double m = (double)fmx[wsid][mys][i];
+    const double m = (double)fmx[wsid][i];
     const double d0 = a0[i] - m, d1 = a1[i] - m;
-    const bool n0 = mine && l0 && d0 >= kBootExpCut, n1 = mine && l1 && d1 >= kBootExpCut;
+    const bool n0 = l0 && d0 >= kBootExpCut, n1 = l1 && d1 >= kBootExpCut;
     if (__builtin_amdgcn_ballot_w64(n0 || n1)) {
       a0[i] = n0 ? exp_tab(d0, etab) : 0.0;
       a1[i] = n1 ? exp_tab(d1, etab) : 0.0;
@@ -2997,33 +2922,26 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
     if (m2 == 0 && live) tsum[slot * NB + i] = ps;
   }
   wave_sync();
-  {
-    // lanes 0..NB-1: slab A's boots, 32..32+NB-1: slab B's; S over the slab's tiles in tile order
-    const int sl = lane >> 5, b = lane & 31;
-    if (sl < nsl && b < NB && !((failm >> sl) & 1)) {
-      const unsigned dn = sl ? doneB : doneA;
-      double S = 0.0;
-      for (unsigned mm = dn; mm; mm &= mm - 1) {
-        const int t = __builtin_ffs((int)mm) - 1;
-        int sslot = 0;
+  if (lane < NB) {  // lane b: boot b's sum S over the slab's tiles in tile order
+    double S = 0.0;
+    for (unsigned mm = done; mm; mm &= mm - 1) {
+      const int t = __builtin_ffs((int)mm) - 1;
+      int sslot = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bool js = pr && j >= 2;
-          if (tl[j] == (t >> 1) && (pr ? (j & 1) : j) < nsel && (int)js == sl) sslot = 2 * j + (t & 1);
-        }
-        S += tsum[sslot * NB + b];
-      }
-      finv[sl * 32 + b] = ((sl ? b0B : b0A) + b < nboot) ? 1.0 / (S * norm_mult) : 0.0;
+      for (int j = 0; j < 4; ++j)
+        if (tl[j] == (t >> 1) && j < nsel) sslot = 2 * j + (t & 1);
+      S += tsum[sslot * NB + lane];
     }
+    finv[lane] = (b0 + lane < nboot) ? 1.0 / (S * norm_mult) : 0.0;
   }
   wave_sync();
-  if (mine) {
-    double* prow = part + (long long)(mys ? pB : pA) * part_stride + (long long)g * GS;
+  {
+    double* prow = part + (long long)p * part_stride + (long long)g * GS;
     double j0 = 0.0, j1 = 0.0;
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      j0 = fma(a0[i], finv[mys * 32 + i], j0);
-      j1 = fma(a1[i], finv[mys * 32 + i], j1);
+      j0 = fma(a0[i], finv[i], j0);
+      j1 = fma(a1[i], finv[i], j1);
     }
     if (l1)
       *reinterpret_cast<d2_t*>(prow + k0) = d2_t{j0, j1};
@@ -3031,25 +2949,24 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
       prow[k0] = j0;
   }
   // tiles not computed stay unwritten: k_sum_partials reads only the tiles in pmask
-  if (lane < nsl && !((failm >> lane) & 1)) {
-    const unsigned dn = lane ? doneB : doneA;
-    pmask[(long long)g * P + (lane ? pB : pA)] = dn;
+  if (lane == 0) {
+    pmask[(long long)g * P + p] = done;
     if (stats) {
       atomicAdd(&stats[0], 1);
-      atomicAdd(&stats[1], __builtin_popcount(dn));
+      atomicAdd(&stats[1], __builtin_popcount(done));
       atomicAdd(&stats[2], NT);
-      atomicAdd(&stats[6 + __builtin_popcount(dn)], 1);
+      atomicAdd(&stats[6 + __builtin_popcount(done)], 1);
     }
   }
 }
 
 
 // ------------------------------------------------------------------ gene-block tile bootstrap
-// k_boot_gene: k_boot_tiles' arithmetic with one 4-wave block per (gene, group of up to SG
-// slabs) instead of one wave per (gene, slab) computing a fixed four bound tiles.  At config 3 a
-// slab needs about three of its thirteen 32-point bound tiles (2: 19%, 3: 79%,
-// 4: 2%), so four tiles per slab compute 25% more rows than needed.  Here the block's 16 rows
-// (4 waves x 4 sixteen-lane rows, each one (slab, bound tile)) are shared by the group's slabs:
+// k_boot_gene: the tile bootstrap's first pass, one 4-wave block per (gene, group of up to SG
+// slabs).  At config 3 a slab needs about three of its thirteen 32-point bound tiles (DESIGN.md
+// §4.0: 2: 19%, 3: 79%, 4: 2%), so a fixed four tiles per slab (k_boot_tiles' plan) would compute
+// 25% more rows than needed.  Here the block's 16 rows (4 waves x 4 sixteen-lane rows, each one
+// (slab, bound tile)) are shared by the group's slabs:
 //   1. bounds: wave w computes the group's boot window 32 w .. 32 w + 31 (tile_bound_pass;
 //      4 windows = 128 boots >= 5 slabs x 20: one bound pass per 32 boots, not per 20) into LDS;
 //   2. plan: per slab its bound tiles ranked by their largest bound over the live boots; every
@@ -3139,9 +3056,10 @@ constexpr int kGeneSlabs = 8;     // slabs per group at most (K >= 2 rows each)
 #else
 #define GENE_EXP(d) exp_tab(d, etab)
 #endif
-// WB waves per block (4, or 3 for wide calls whose slabs mostly need two tiles: 12 rows for 5
-// slabs).  With 3 waves the fourth 32-boot bound window is split by entry chunks over the
-// three waves (tile_bound_partial, exact int64 sums in LDS), so no wave does two passes.
+// WB waves per block: the launcher instantiates 4 only.  The kernel text still accepts 3 (12
+// rows for 5 slabs, for wide calls whose slabs mostly need two tiles): the fourth 32-boot bound
+// window is then split by entry chunks over the three waves (tile_bound_partial, exact int64
+// sums in LDS), so no wave does two passes.  No build instantiates that form.
 template <int NB, int WB>
 __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TILE_WPE))) void k_boot_gene(
     const double* __restrict__ D, const int2* __restrict__ ent, const int* __restrict__ nnz, int ent_stride,
@@ -3552,8 +3470,7 @@ template __global__ void k_boot_tiles<20, 1>(const double* __restrict__, const i
                                              double* __restrict__, long long, int* __restrict__, int,
                                              const unsigned char* __restrict__, int, const unsigned* __restrict__,
                                              const int* __restrict__, const int* __restrict__, int, int* __restrict__,
-                                             int* __restrict__, const int* __restrict__, unsigned* __restrict__,
-                                             const int* __restrict__);
+                                             int* __restrict__, unsigned* __restrict__, const int* __restrict__);
 #endif
 
 // jp[g, k] = sum over slabs p (in order) of part[p][g][k]
@@ -4425,48 +4342,16 @@ hipError_t launch_widen16(const unsigned short* in, int* out, size_t n, hipStrea
   return hipGetLastError();
 }
 
-// cell chunks of launch_ell: enough (gene tile, chunk) blocks to fill the chip twice, whole
-// 64-cell steps, at most kEllMaxChunks
-static void ell_chunks(int ngenes, int ncells, int max_chunks, int* ccells, int* nchk) {
-  const long long gt = std::max<long long>(1, div_up(ngenes, 64)), steps = std::max<long long>(1, div_up(ncells, 64));
-  long long k = std::min<long long>({div_up(1024, gt), steps, kEllMaxChunks});
-  if (max_chunks > 0) k = std::min<long long>(k, max_chunks);
-  k = std::max<long long>(1, k);
-  const long long cc = div_up(steps, k) * 64;
-  *ccells = (int)cc;
-  *nchk = (int)std::max<long long>(1, div_up(ncells, cc));
-}
-
-size_t ell_work_bytes(int ngenes, int ncells, int max_chunks) {
-  int cc, k;
-  ell_chunks(ngenes, ncells, max_chunks, &cc, &k);
-  return k > 1 ? sizeof(unsigned) * 2 * (size_t)k * std::max(ngenes, 1) : 0;
-}
-
 hipError_t launch_ell(const int* uci, long long ld_uci, int ngenes, int ncells, const long long* ucl_off,
                       const int* base_col, int stride, int pad_col, int padto, int2* ent, int* nnz, hipStream_t s,
-                      int cell_off, void* work, const int* ucl, unsigned* key, int* idx, int kg0, int kgn, int kch,
-                      int desc, int max_chunks) {
+                      int cell_off, const int* ucl, unsigned* key, int* idx, int kg0, int kgn, int kch, int desc) {
   if (ngenes <= 0) return hipSuccess;
   if (padto == 64 ? stride < ((ncells + 63) & ~63) + 8 || stride < 72 : stride < ((ncells + 7) & ~7) + 8)
     return hipErrorInvalidValue;
   if (cell_off < 0) return hipErrorInvalidValue;
   if (key && (!ucl || !idx || kch < 1 || kgn < kg0 + ngenes || kch > kgn)) return hipErrorInvalidValue;
-  int cc, k;
-  ell_chunks(ngenes, ncells, max_chunks, &cc, &k);
-  unsigned* cnt = nullptr;
-  unsigned* ksum = nullptr;
-  if (k > 1) {
-    if (!work) return hipErrorInvalidValue;
-    cnt = static_cast<unsigned*>(work);
-    ksum = cnt + (size_t)k * ngenes;
-    hipLaunchKernelGGL(k_ell<false>, dim3(div_up(ngenes, 64), k), dim3(64 * kEllWaves), 0, s, uci, ld_uci, ngenes,
-                       ncells, ucl_off, base_col, stride, pad_col, padto, ent, nnz, cell_off, cc, k, cnt, ksum, ucl,
-                       key, idx, kg0, kgn, kch, desc);
-  }
-  hipLaunchKernelGGL(k_ell<true>, dim3(div_up(ngenes, 64), k), dim3(64 * kEllWaves), 0, s, uci, ld_uci, ngenes, ncells,
-                     ucl_off, base_col, stride, pad_col, padto, ent, nnz, cell_off, cc, k, cnt, ksum, ucl, key, idx,
-                     kg0, kgn, kch, desc);
+  hipLaunchKernelGGL(k_ell, dim3(div_up(ngenes, 64)), dim3(64 * kEllWaves), 0, s, uci, ld_uci, ngenes, ncells, ucl_off,
+                     base_col, stride, pad_col, padto, ent, nnz, cell_off, ucl, key, idx, kg0, kgn, kch, desc);
   return hipGetLastError();
 }
 
@@ -4702,29 +4587,24 @@ hipError_t launch_boot_tiles(const Boot2Args& a, const TileBootArgs& tb, hipStre
   if ((long long)a.ncols_p1 * a.GS >= (1LL << 31) || (long long)a.ncells * a.Bp >= (1LL << 31) ||
       (long long)a.ncells * 32 * P >= (1LL << 31))
     return hipErrorInvalidValue;
+  // gene blocks: one 4-wave block per (gene, group of SG slabs) shares 16 rows among the group's
+  // slabs; the slabs whose post-check fails take the four-tile pass over `wide`
+  if (!tb.W8g || !tb.wide || tb.SG < 1 || tb.SG > kGeneSlabs || tb.SG * a.nb > 128) return hipErrorInvalidValue;
+  const int NGR = (P + tb.SG - 1) / tb.SG;
+  if ((long long)a.ncells * NGR * 128 >= (1LL << 31) || tb.Bq < (NGR - 1) * tb.SG * a.nb + 128)
+    return hipErrorInvalidValue;
+  // the launch's genes (a gene chunk, or every gene)
+  const int g_lo = tb.g_hi >= 0 ? tb.g_lo : 0, g_hi = tb.g_hi >= 0 ? tb.g_hi : a.ngenes;
+  if (g_lo < 0 || g_hi > a.ngenes || g_lo > g_hi) return hipErrorInvalidValue;
+  const long long gspan = g_hi - g_lo;
   // redo: [items] fallback flags, [1] the fallback list's length, [items] the list; and the list
-  // pass's count wide[0] (below): one zeroing launch
+  // pass's count wide[0]: one zeroing launch
   ZeroSpans z{};
   z.p[z.count] = a.redo;
   z.n[z.count++] = sizeof(int) * ((size_t)a.ngenes * P + 1);
+  z.p[z.count] = tb.wide;
+  z.n[z.count++] = sizeof(int);
   const long long items = (long long)a.ngenes * P;
-  // gene blocks: one 4-wave block per (gene, group of SG slabs) shares 16 rows among the group's
-  // slabs; the slabs whose post-check fails take the four-tile pass over `wide` (without the gene
-  // block arguments: one k_boot_tiles wave per slab)
-  const bool gene = tb.gene && tb.W8g && tb.wide && tb.SG >= 1 && tb.SG <= kGeneSlabs && tb.SG * a.nb <= 128;
-  if (gene) {
-    const int NGR = (P + tb.SG - 1) / tb.SG;
-    if ((long long)a.ncells * NGR * 128 >= (1LL << 31) || tb.Bq < (NGR - 1) * tb.SG * a.nb + 128) return hipErrorInvalidValue;
-  }
-  // the launch's genes (a gene chunk with gene blocks; every gene otherwise)
-  const int g_lo = tb.g_hi >= 0 ? tb.g_lo : 0, g_hi = tb.g_hi >= 0 ? tb.g_hi : a.ngenes;
-  if (g_lo < 0 || g_hi > a.ngenes || g_lo > g_hi || ((g_lo != 0 || g_hi != a.ngenes) && !gene))
-    return hipErrorInvalidValue;
-  const long long gspan = g_hi - g_lo;
-  if (gene) {
-    z.p[z.count] = tb.wide;
-    z.n[z.count++] = sizeof(int);
-  }
   hipError_t e = launch_zero(z, s);
   if (e != hipSuccess) return e;
   constexpr int WB = 4;
@@ -4734,29 +4614,22 @@ hipError_t launch_boot_tiles(const Boot2Args& a, const TileBootArgs& tb, hipStre
   // counting past it), and the list pass's grid of items2 / WB blocks must then hold no wave whose
   // index lies in [cap, grid * WB) -- such a wave would read an entry this call never wrote.
   const long long gene_cap = std::max<long long>(WB, ((tb.list_cap > 0 ? tb.list_cap : 16384) / WB) * WB);
-  const long long items2 = gene ? std::min(gspan * P, gene_cap) : 0;
-  const long long gblocks = gene ? gspan * ((P + tb.SG - 1) / tb.SG) : 0;
-  const long long gblk0 = gene ? (long long)g_lo * ((P + tb.SG - 1) / tb.SG) : 0;
+  const long long items2 = std::min(gspan * P, gene_cap);
+  const long long gblocks = gspan * NGR;
+  const long long gblk0 = (long long)g_lo * NGR;
   // gene blocks holding all of a gene's slabs write the finished jp rows of their genes themselves
-  int* const gdone = (gene && tb.gdone && tb.SG >= P) ? tb.gdone : nullptr;
-#define SCDE_BT(NBV)                                                                                              \
-  case NBV:                                                                                                        \
-    if (gene) {                                                                                                    \
-      hipLaunchKernelGGL((k_boot_gene<NBV, 4>), dim3((unsigned)gblocks), dim3(256), 0, s, a.D, a.ent, a.nnz,      \
-                         a.ent_stride, a.Wt, a.Bp, a.ncells, a.wset, a.Z, a.G, a.GS, P, tb.SG, a.nboot,          \
-                         a.norm_mult, a.degen_thresh, a.part, a.part_stride, a.degen, a.ngenes, tb.W8g, tb.Bq,  \
-                         tb.UQ, tb.ZUq, tb.nanflag, tb.maxgroups, tb.kcap, a.redo, tb.stats, tb.order, tb.pmask, \
-                         tb.wide, (int)items2, (int)gblk0, a.out, a.out_g, a.out_k, gdone);                      \
-      hipLaunchKernelGGL((k_boot_tiles<NBV, WB>), dim3((unsigned)div_up(items2, WB)), dim3(64 * WB), 0, s, a.D,   \
-                         a.ent, a.nnz, a.ent_stride, a.Wt, a.Bp, a.ncells, a.wset, a.Z, a.G, a.GS, P, a.nboot,    \
-                         a.norm_mult, a.degen_thresh, a.part, a.part_stride, a.degen, a.ngenes, tb.W8p, tb.Bq,    \
-                         tb.UQ, tb.ZUq, tb.nanflag, tb.maxgroups, a.redo, tb.stats, tb.order, tb.pmask, tb.wide); \
-    } else {                                                                                                       \
-      hipLaunchKernelGGL((k_boot_tiles<NBV, WB>), dim3((unsigned)div_up(items, WB)), dim3(64 * WB), 0, s, a.D,    \
-                         a.ent, a.nnz, a.ent_stride, a.Wt, a.Bp, a.ncells, a.wset, a.Z, a.G, a.GS, P, a.nboot,    \
-                         a.norm_mult, a.degen_thresh, a.part, a.part_stride, a.degen, a.ngenes, tb.W8p, tb.Bq,    \
-                         tb.UQ, tb.ZUq, tb.nanflag, tb.maxgroups, a.redo, tb.stats, tb.order, tb.pmask, nullptr); \
-    }                                                                                                              \
+  int* const gdone = (tb.gdone && tb.SG >= P) ? tb.gdone : nullptr;
+#define SCDE_BT(NBV)                                                                                            \
+  case NBV:                                                                                                      \
+    hipLaunchKernelGGL((k_boot_gene<NBV, 4>), dim3((unsigned)gblocks), dim3(256), 0, s, a.D, a.ent, a.nnz,      \
+                       a.ent_stride, a.Wt, a.Bp, a.ncells, a.wset, a.Z, a.G, a.GS, P, tb.SG, a.nboot,          \
+                       a.norm_mult, a.degen_thresh, a.part, a.part_stride, a.degen, a.ngenes, tb.W8g, tb.Bq,  \
+                       tb.UQ, tb.ZUq, tb.nanflag, tb.maxgroups, tb.kcap, a.redo, tb.stats, tb.order, tb.pmask, \
+                       tb.wide, (int)items2, (int)gblk0, a.out, a.out_g, a.out_k, gdone);                      \
+    hipLaunchKernelGGL((k_boot_tiles<NBV, WB>), dim3((unsigned)div_up(items2, WB)), dim3(64 * WB), 0, s, a.D,   \
+                       a.ent, a.nnz, a.ent_stride, a.Wt, a.Bp, a.ncells, a.wset, a.Z, a.G, a.GS, P, a.nboot,    \
+                       a.norm_mult, a.degen_thresh, a.part, a.part_stride, a.degen, a.ngenes, tb.W8p, tb.Bq,    \
+                       tb.UQ, tb.ZUq, tb.nanflag, tb.maxgroups, a.redo, tb.stats, tb.pmask, tb.wide);           \
     break;
   switch (a.nb) {
     SCDE_BT(4) SCDE_BT(8) SCDE_BT(12) SCDE_BT(16) SCDE_BT(20)
@@ -4919,18 +4792,10 @@ hipError_t launch_ratio_summary(const RatioArgs& a, hipStream_t s) {
   if (a.ngenes <= 0) return hipSuccess;
   const int NA = (a.n + 9) & ~1;
   const size_t shm = sizeof(double) * (size_t)(4 * NA + 2 + ((2 * a.n - 1 + 49) & ~1) + 16) + sizeof(int) * 32;
-  // R = 4 by default: a 4-step unrolled loop rotates the R-wide register window fully (no
-  // moves); measured fastest of R = 4, 5, 8 at n = 401
+  // R = 4: a 4-step unrolled loop rotates the R-wide register window fully (no moves);
+  // measured fastest of R = 4, 5, 8 at n = 401, in blocks of 128 threads
   const int grid = a.ngenes < 65536 ? a.ngenes : 65536;
-  int rsel = a.window, bsel = a.block;  // tuning options of the context (scde_ctx_set_option)
-  if (rsel != 4 && rsel != 5 && rsel != 7 && rsel != 8) rsel = 4;
-  if (bsel != 64 && bsel != 128 && bsel != 256) bsel = 128;
-  switch (rsel) {
-    case 7: hipLaunchKernelGGL(k_ratio_summary<7>, dim3(grid), dim3(bsel), shm, s, a); break;
-    case 8: hipLaunchKernelGGL(k_ratio_summary<8>, dim3(grid), dim3(bsel), shm, s, a); break;
-    case 5: hipLaunchKernelGGL(k_ratio_summary<5>, dim3(grid), dim3(bsel), shm, s, a); break;
-    default: hipLaunchKernelGGL(k_ratio_summary<4>, dim3(grid), dim3(bsel), shm, s, a); break;
-  }
+  hipLaunchKernelGGL(k_ratio_summary<4>, dim3(grid), dim3(128), shm, s, a);
   return hipGetLastError();
 }
 

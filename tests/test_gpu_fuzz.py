@@ -8,7 +8,9 @@ counts from a zero-inflated negative binomial with occasional huge counts, model
 resampled from the es.mef (6-column) or knn (12-column: local theta, squared-logit
 concentration) fixtures, n.randomizations in {1, 2, 7, 20, 33}, n.cores in {1, 2, 5},
 prior length.out in {60, 401}.  Every case runs through the bootstrap kernels: k_boot2 (or
-the tile path from 400 cells), and the tile path at every size (boot_tiles_cells 0).
+the tile path from 400 cells), the tile path at every size (boot_tiles_cells 0), and the tile
+path with gene blocks of one row per slab (gene_rows 1), which leaves every slab that needs more
+rows to the four-tile list pass: partly live last slabs, single slabs, grids of two bound tiles.
 """
 import numpy as np
 import pytest
@@ -42,7 +44,8 @@ def _case(seed):
         length_out=int(rng.choice([60, 400])))
 
 
-@pytest.mark.parametrize("opts", [{}, {"boot_tiles_cells": 0}], ids=["default", "tiles"])
+@pytest.mark.parametrize("opts", [{}, {"boot_tiles_cells": 0}, {"boot_tiles_cells": 0, "gene_rows": 1}],
+                         ids=["default", "tiles", "list-pass"])
 @pytest.mark.parametrize("seed", range(NCASES))
 def test_expression_difference_fuzz(seed, opts):
     from oracle import oracle as O
@@ -61,6 +64,7 @@ def test_expression_difference_fuzz(seed, opts):
                                              return_posteriors=True)
     finally:
         ctx.set_option("boot_tiles_cells", 400)
+        ctx.set_option("gene_rows", 4)
     # the oracle takes factor codes (level order a < b, NA = -1), the api R-style labels
     codes = np.array([{"a": 0, "b": 1, None: -1}[v] for v in glist])
     ref = O.scde_expression_difference(models, counts, prior["x"], prior["y"], codes,
