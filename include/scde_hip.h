@@ -553,6 +553,83 @@ int scde_gather_cols_dev(scde_ctx* ctx, const double* x_dev, int nrow, int64_t n
 int scde_sigma1sq_batch_dev(scde_ctx* ctx, const double* x_dev, int ncells, int64_t ngenes, int nprob,
                             const int64_t* off, const int* idx, double* out);
 
+/* ---------------------------------------------------------------- aspect redundancy reduction
+ * The numerical pieces of pagoda.reduce.loading.redundancy (R/functions.R:2490-2526) and
+ * pagoda.reduce.redundancy (2559-2610) with their helpers pathway.pc.correlation.distance
+ * (5126-5164) and collapse.aspect.clusters (5166-5198); csrc/aspects.hip, chained by
+ * scde_amd/aspects.py.  m aspects.  Square matrices are m x m column-major and resident in HBM;
+ * the patterns x (tam$xv) and their weights w (tam$xvw) are resident as ncells x m column-major
+ * (an aspect's cells contiguous), the layout scde_cor_distance_dev takes.  ctx may be NULL.
+ * Argument errors are SCDE_EARG with a message naming the offending item. */
+
+/* scde_plSemicompleteCor2 on host lists, leaving r (m x m doubles) and n (m x m ints) in HBM. */
+int scde_plSemicompleteCor2_dev(scde_ctx* ctx, int np, const int64_t* off, const int* idx, const double* val,
+                                double* r_dev, int* n_dev);
+
+/* The Student-t renormalisation of loading correlations to target_ndf degrees of freedom
+ * (R/functions.R:5146-5157).  For a pair with correlation r and union size n, nu = n - 2:
+ *   tv = r sqrt(nu / (1 - r^2)),  z = pt(tv, nu, lower = F, log = T),
+ *   nr = qt(z, target_ndf - 2, lower = F, log = T),  cr = nr / sqrt(target_ndf - 2 + nr^2).
+ * In correlation space p = I_{1 - r^2}(nu / 2, 1/2) / 2 and |cr| solves
+ * I_{1 - cr^2}((target_ndf - 2) / 2, 1/2) / 2 = p, sign(cr) = sign(r): an odd map, evaluated in
+ * log space (the smaller of the tail p and the central mass 1/2 - p is matched as a logarithm),
+ * so tails far below 1e-308 stay finite.  cr = r exactly when n <= 2, |r| >= 1 or r is NaN;
+ * r = 0 gives 0; n = target_ndf gives r to rounding.  One deviation from R: R's double evaluation
+ * loses the negative side once exp(log p) underflows and falls back to r there; the odd map is
+ * used everywhere.
+ * Only the pairs above the diagonal (r[i + j m], n[i + j m], i < j) are read and transformed, one
+ * lane per pair, the result written to both triangles of cr; cr's diagonal is r's.  FP64, no
+ * fast-math.  target_ndf must be finite and above 2; m >= 1.  cr_dev must not be r_dev. */
+int scde_t_renorm_dev(scde_ctx* ctx, const double* r_dev, const int* n_dev, int m, double target_ndf,
+                      double* cr_dev);
+/* The same on host matrices (staged; SCDE_EHIP "out of memory" before any launch). */
+int scde_t_renorm_host(scde_ctx* ctx, const double* r, const int* n, int m, double target_ndf, double* cr);
+
+/* The distance between aspects from their patterns.  c = the Pearson correlation of the m columns
+ * of x_dev: each column centred and scaled to unit length (two passes), then their Gram matrix
+ * on the FP64 matrix cores; NaN for a column that holds a single value (cor() gives NA).
+ *   cr_dev given (m x m, from scde_t_renorm_dev or r itself):
+ *     pclc = max(0, 1 - |cr|);  cda = |c| (abs) or max(c, 0);  d1 = 1 - cda;
+ *     out = (1 - sqrt((1 - pclc) * (1 - d1)))^corr_power          (R/functions.R:2491-2499)
+ *   cr_dev NULL:  out = 1 - |c| (abs) or 1 - c                     (R/functions.R:2571-2575)
+ * each expression in float64 as written.  Both triangles are written, the diagonal exactly 0.
+ * SCDE_EHIP "out of memory", before any launch, when the scaled copy of the patterns (ncells x m
+ * doubles) cannot be allocated. */
+int scde_aspect_distance_dev(scde_ctx* ctx, const double* x_dev, int ncells, int m, const double* cr_dev, int abs,
+                             double corr_power, double* out_dev);
+
+/* 1 - c or 1 - |c| (abs) of c = scde_matWCorr of the patterns with their weights
+ * (R/functions.R:2562-2568), both triangles, the diagonal exactly 0. */
+int scde_matWCorr_distance_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev, int ncells, int m, int abs,
+                               double* out_dev);
+
+/* collapse.aspect.clusters.  Cluster p is the rows idx[off[p] .. off[p + 1]) (host lists, at
+ * least one row each) of x_dev / w_dev; column p of d_dev / dw_dev (ncells x nclust, resident)
+ * receives its pattern and weights.  One launch, one workgroup per cluster.
+ *   weights   colSums(w[rows, ] * sd(row)) / their sum (sd = sqrt of R's var, denominator
+ *             ncells - 1), for every cluster
+ *   pattern   one row: that row.  pick_top: the row of largest variance (first maximum).
+ *             Otherwise, with X the rows transposed and each column centred (ncells x k): v1 its
+ *             unit top right singular vector, xv = X v1; a = the per-cell mean over the rows of
+ *             (uncentred row) * |v1_i|; xv is negated when cor(xv, a) < 0; with scale,
+ *             xv = xv * sqrt(max row var) / sqrt(var(xv)).  v1 comes from the Gram matrix of the
+ *             smaller side (k or ncells) on the FP64 matrix cores, Householder
+ *             tridiagonalisation, Sturm bisection of the largest eigenvalue, inverse iteration
+ *             on the tridiagonal matrix and the back-transformation; when ncells < k the
+ *             cell-side eigenvector times sigma_1 is xv.
+ * Per cluster, to the host: top[p] = the row of largest variance (first maximum; the row itself
+ * for one row); fallback[p] = 1 when sum|diff(xv)| == 0, or sum|xv| == 0 after scaling -- the
+ * caller replaces the pattern by |rnorm(ncells, sd = 1e-6)| -- else 0; orientation[p] =
+ * cor(xv, a) after the flip (>= 0), NaN for one row, pick_top and fallback clusters.  A non-finite
+ * orientation of a cluster that is not a fallback is where R stops.
+ * No atomics: results are bit-repeatable and depend on the cluster alone.  Row indices are
+ * checked on the host (SCDE_EARG naming the cluster) and again on the device before any is used.
+ * ncells >= 2.  SCDE_EHIP "out of memory", before the launch, when the workspace (sum over
+ * clusters of min(rows, ncells)^2 + O(rows + ncells) doubles) cannot be allocated. */
+int scde_collapse_aspects_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev, int ncells, int m, int nclust,
+                              const int64_t* off, const int* idx, int scale, int pick_top, double* d_dev,
+                              double* dw_dev, int* top, int* fallback, double* orientation);
+
 /* Free and total bytes of the context's device (hipMemGetInfo). */
 int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);
 

@@ -32,6 +32,8 @@ EXPORTS = [
     "scde_hclust_host", "scde_hclust_dev", "scde_hclust_batch_dev", "scde_cor_distance_dev",
     "scde_r_norm_rand", "scde_r_mt_words", "scde_rnorm_matrix_dev", "scde_winsorize_dev", "scde_keep_absdiff_dev",
     "scde_gather_cols_dev", "scde_sigma1sq_batch_dev", "scde_dev_mem_info",
+    "scde_plSemicompleteCor2_dev", "scde_t_renorm_dev", "scde_t_renorm_host", "scde_aspect_distance_dev",
+    "scde_matWCorr_distance_dev", "scde_collapse_aspects_dev",
 ]
 
 
@@ -144,6 +146,11 @@ def lib():
     L.scde_gather_cols_dev.argtypes = [P, P, i, i64, P, i, P]
     L.scde_sigma1sq_batch_dev.argtypes = [P, P, i, i64, i, P, P, P]
     L.scde_dev_mem_info.argtypes = [P, P, P]
+    L.scde_plSemicompleteCor2_dev.argtypes = [P, i, P, P, P, P, P]
+    L.scde_t_renorm_dev.argtypes = L.scde_t_renorm_host.argtypes = [P, P, P, i, d, P]
+    L.scde_aspect_distance_dev.argtypes = [P, P, i, i, P, i, d, P]
+    L.scde_matWCorr_distance_dev.argtypes = [P, P, P, i, i, i, P]
+    L.scde_collapse_aspects_dev.argtypes = [P, P, P, i, i, i, P, P, i, i, P, P, P, P, P]
     _lib = L
     return L
 

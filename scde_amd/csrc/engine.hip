@@ -267,6 +267,9 @@ struct scde_ctx {
   // the random rounds of pagoda.gene.clusters: raw twister words, keep flags / column lists,
   // sigma1's problem lists, workspace and results
   Buf gr_raw, gr_int, gr_prob, gr_ws, gr_out;
+  // aspect redundancy reduction (aspects.hip): staged host matrices (r, n, cr), the patterns
+  // scaled to unit length, the collapse kernel's cluster lists, workspace and per-cluster results
+  Buf as_r, as_n, as_cr, as_z, as_prob, as_ws, as_out;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters
@@ -579,6 +582,7 @@ struct scde_ctx {
                  &ds_x,     &ds_u,       &ds_f,    &ds_p,      &ds_x0,     &ds_cell,   &ds_jpm,   &ds_out,
                  &hc_in,    &hc_ws,      &hc_prob, &hc_out,
                  &gr_raw,   &gr_int,     &gr_prob, &gr_ws,     &gr_out,
+                 &as_r,     &as_n,       &as_cr,   &as_z,      &as_prob,   &as_ws,     &as_out,
                  &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &excd, &gdone};
     for (Buf* b : wp) b->release();
     for (auto& u : us) u.release();
@@ -4723,6 +4727,170 @@ int scde_sigma1sq_batch_dev(scde_ctx* ctx, const double* x_dev, int ncells, int6
   if (sizeof(double) * wsd > ((size_t)1 << 30)) ctx->gr_ws.release();
   for (int p = 0; p < nprob; ++p)
     if (hf[p] != 0) return fail(SCDE_EINTERNAL, "sigma1sq: problem %d: a column index failed the device check", p);
+  return SCDE_OK;
+}
+
+// ------------------------------------------------------------------ aspect redundancy reduction
+// pagoda.reduce.loading.redundancy / pagoda.reduce.redundancy and their helpers (aspects.hip;
+// contract in scde_hip.h).  Arguments are checked before the GPU is touched.
+static int plcor_lists_check(int np, const int64_t* off, const int* idx, const double* val) {
+  if (np < 1 || !off || !idx || !val) return fail(SCDE_EARG, "plSemicompleteCor2: null argument or no lists");
+  if (off[0] != 0) return fail(SCDE_EARG, "plSemicompleteCor2: off[0] must be 0");
+  for (int p = 0; p < np; ++p) {
+    if (off[p + 1] < off[p]) return fail(SCDE_EARG, "plSemicompleteCor2: list %d has a negative length", p);
+    for (int64_t e = off[p] + 1; e < off[p + 1]; ++e)
+      if (idx[e] <= idx[e - 1]) return fail(SCDE_EARG, "plSemicompleteCor2: list %d: gene indices must increase", p);
+  }
+  return SCDE_OK;
+}
+
+int scde_plSemicompleteCor2_dev(scde_ctx* ctx, int np, const int64_t* off, const int* idx, const double* val,
+                                double* r_dev, int* n_dev) {
+  FORK_GUARD();
+  if (!r_dev || !n_dev) return fail(SCDE_EARG, "plSemicompleteCor2: null output");
+  RCHK(plcor_lists_check(np, off, idx, val));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  const size_t tot = (size_t)off[np];
+  std::vector<long long> offl(off, off + np + 1);
+  HCHK(upload(ctx->pg_a, offl.data(), offl.size(), ctx->stream));
+  HCHK(upload(ctx->pg_b, idx, std::max<size_t>(tot, 1), ctx->stream));
+  HCHK(upload(ctx->pg_c, val, std::max<size_t>(tot, 1), ctx->stream));
+  HCHK(launch_plcor(np, ctx->pg_a.as<long long>(), ctx->pg_b.as<int>(), ctx->pg_c.as<double>(), r_dev, n_dev,
+                    ctx->stream));
+  return ctx->sync();  // (offl is read by the copy until here)
+}
+
+static int t_renorm_check(const void* r, const void* n, int m, double target_ndf, const void* cr) {
+  if (!r || !n || !cr) return fail(SCDE_EARG, "t_renorm: null argument");
+  if (m < 1) return fail(SCDE_EARG, "t_renorm: m must be at least 1 (m = %d)", m);
+  if (!(target_ndf > 2.0) || !(target_ndf < 1e15))
+    return fail(SCDE_EARG, "t_renorm: target_ndf must be above 2 and finite (target_ndf = %g)", target_ndf);
+  return SCDE_OK;
+}
+
+int scde_t_renorm_dev(scde_ctx* ctx, const double* r_dev, const int* n_dev, int m, double target_ndf,
+                      double* cr_dev) {
+  FORK_GUARD();
+  RCHK(t_renorm_check(r_dev, n_dev, m, target_ndf, cr_dev));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_t_renorm(r_dev, n_dev, m, target_ndf, cr_dev, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return ctx->sync();
+}
+
+int scde_t_renorm_host(scde_ctx* ctx, const double* r, const int* n, int m, double target_ndf, double* cr) {
+  FORK_GUARD();
+  RCHK(t_renorm_check(r, n, m, target_ndf, cr));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  const size_t nn = (size_t)m * m;
+  if (ctx->as_r.ensure(sizeof(double) * nn) != hipSuccess || ctx->as_cr.ensure(sizeof(double) * nn) != hipSuccess ||
+      ctx->as_n.ensure(sizeof(int) * nn) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "t_renorm: out of memory: three %d x %d matrices need %zu bytes of device memory", m, m,
+                (2 * sizeof(double) + sizeof(int)) * nn);
+  }
+  HCHK(hipMemcpyAsync(ctx->as_r.p, r, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(hipMemcpyAsync(ctx->as_n.p, n, sizeof(int) * nn, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(launch_t_renorm(ctx->as_r.as<double>(), ctx->as_n.as<int>(), m, target_ndf, ctx->as_cr.as<double>(),
+                       ctx->stream));
+  HCHK(hipMemcpyAsync(cr, ctx->as_cr.p, sizeof(double) * nn, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_aspect_distance_dev(scde_ctx* ctx, const double* x_dev, int ncells, int m, const double* cr_dev, int abs,
+                             double corr_power, double* out_dev) {
+  FORK_GUARD();
+  if (!x_dev || !out_dev) return fail(SCDE_EARG, "aspect_distance: null argument");
+  if (ncells < 1 || m < 1) return fail(SCDE_EARG, "aspect_distance: bad dimensions (ncells = %d, m = %d)", ncells, m);
+  if (cr_dev && !(corr_power == corr_power))
+    return fail(SCDE_EARG, "aspect_distance: corr_power is NaN");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  if (ctx->as_z.ensure(sizeof(double) * (size_t)ncells * m) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "aspect_distance: out of memory: the scaled patterns need %zu bytes of device memory",
+                sizeof(double) * (size_t)ncells * m);
+  }
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_aspect_dist(x_dev, ncells, m, ctx->as_z.as<double>(), cr_dev, abs != 0, corr_power, out_dev,
+                          ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return ctx->sync();
+}
+
+int scde_matWCorr_distance_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev, int ncells, int m, int abs,
+                               double* out_dev) {
+  FORK_GUARD();
+  if (!x_dev || !w_dev || !out_dev) return fail(SCDE_EARG, "matWCorr_distance: null argument");
+  if (ncells < 1 || m < 1)
+    return fail(SCDE_EARG, "matWCorr_distance: bad dimensions (ncells = %d, m = %d)", ncells, m);
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_matwcorr(x_dev, w_dev, ncells, m, out_dev, ctx->stream));
+  HCHK(launch_wdist(out_dev, m, abs != 0, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return ctx->sync();
+}
+
+int scde_collapse_aspects_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev, int ncells, int m, int nclust,
+                              const int64_t* off, const int* idx, int scale, int pick_top, double* d_dev,
+                              double* dw_dev, int* top, int* fallback, double* orientation) {
+  FORK_GUARD();
+  if (nclust < 0) return fail(SCDE_EARG, "collapse: nclust must not be negative");
+  if (nclust == 0) return SCDE_OK;
+  if (!x_dev || !w_dev || !off || !idx || !d_dev || !dw_dev || !top || !fallback || !orientation)
+    return fail(SCDE_EARG, "collapse: null argument");
+  if (ncells < 2) return fail(SCDE_EARG, "collapse: at least 2 cells are needed (ncells = %d)", ncells);
+  if (m < 1) return fail(SCDE_EARG, "collapse: m must be at least 1 (m = %d)", m);
+  if (off[0] < 0) return fail(SCDE_EARG, "collapse: negative offset");
+  std::vector<long long> po(2 * (size_t)nclust + 1);  // off[nclust + 1], then ws_off[nclust]
+  size_t wsd = 0;
+  for (int p = 0; p < nclust; ++p) {
+    const int64_t q = off[p + 1] - off[p];
+    if (q < 1) return fail(SCDE_EARG, "collapse: cluster %d has no rows", p);
+    if (q > m) return fail(SCDE_EARG, "collapse: cluster %d lists %lld rows of %d", p, (long long)q, m);
+    for (int64_t t = off[p]; t < off[p + 1]; ++t)
+      if (idx[t] < 0 || idx[t] >= m)
+        return fail(SCDE_EARG, "collapse: cluster %d: row index %d outside [0, %d)", p, idx[t], m);
+    po[p] = off[p] - off[0];
+    po[nclust + 1 + p] = (long long)wsd;
+    wsd += collapse_ws_doubles(q, ncells, pick_top);
+  }
+  po[nclust] = off[nclust] - off[0];
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  // the workspace comes first: a batch that does not fit fails here, before any launch
+  if (ctx->as_ws.ensure(sizeof(double) * wsd) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "collapse: out of memory: the workspace of %d cluster(s) needs %zu bytes of device memory",
+                nclust, sizeof(double) * wsd);
+  }
+  const size_t nidx = (size_t)(off[nclust] - off[0]);
+  HCHK(ctx->as_prob.ensure(sizeof(long long) * po.size() + sizeof(int) * nidx));
+  long long* d_off = ctx->as_prob.as<long long>();
+  int* d_idx = reinterpret_cast<int*>(d_off + po.size());
+  HCHK(hipMemcpyAsync(d_off, po.data(), sizeof(long long) * po.size(), hipMemcpyHostToDevice, ctx->stream));
+  HCHK(hipMemcpyAsync(d_idx, idx + off[0], sizeof(int) * nidx, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(ctx->as_out.ensure((sizeof(double) + 2 * sizeof(int)) * (size_t)nclust));
+  double* d_cor = ctx->as_out.as<double>();
+  int* d_top = reinterpret_cast<int*>(d_cor + nclust);
+  int* d_st = d_top + nclust;
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_collapse(x_dev, w_dev, ncells, m, nclust, d_off, d_idx, d_off + nclust + 1, ctx->as_ws.as<double>(),
+                       scale != 0, pick_top != 0, d_dev, dw_dev, d_top, d_st, d_cor, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(orientation, d_cor, sizeof(double) * (size_t)nclust, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(top, d_top, sizeof(int) * (size_t)nclust, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(fallback, d_st, sizeof(int) * (size_t)nclust, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  if (sizeof(double) * wsd > ((size_t)1 << 30)) ctx->as_ws.release();
+  for (int p = 0; p < nclust; ++p)
+    if (fallback[p] < 0) return fail(SCDE_EINTERNAL, "collapse: cluster %d: a row index failed the device check", p);
   return SCDE_OK;
 }
 }  // extern "C"

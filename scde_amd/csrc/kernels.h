@@ -462,4 +462,26 @@ hipError_t launch_sigma1sq(const double* x, int ncells, long long ngenes, int np
                            const int* idx, const long long* ws_off, double* ws, double* out, int* flag,
                            hipStream_t s);
 
+// ---- aspect redundancy reduction (aspects.hip; contract in include/scde_hip.h).  Square
+// matrices are m x m column-major; patterns are ncells x m column-major (an aspect contiguous).
+// Student-t renormalisation of the pairs i < j of r (union sizes cnt) to target_ndf, mirrored
+// into cr; cr's diagonal is r's
+hipError_t launch_t_renorm(const double* r, const int* cnt, int m, double target_ndf, double* cr, hipStream_t s);
+// d = the distance from the Pearson correlation c of the m columns of x (ncells x m; z: scratch
+// of the same size): with cr the combined loading x pattern distance, without it 1 - c or
+// 1 - |c|; NaN for a column that holds a single value; both triangles, diagonal 0
+hipError_t launch_aspect_dist(const double* x, int ncells, int m, double* z, const double* cr, int ab, double power,
+                              double* d, hipStream_t s);
+// d (matWCorr's result: the lower triangle) becomes 1 - c or 1 - |c|, both triangles, diagonal 0
+hipError_t launch_wdist(double* d, int m, int ab, hipStream_t s);
+// collapse.aspect.clusters: cluster p = rows idx[off[p] .. off[p + 1]) of x / w, a workspace of
+// collapse_ws_doubles(.) doubles at ws + ws_off[p]; column p of d / wo receives the pattern and
+// the weights.  top[p]: the row of largest variance; status[p]: 0, 1 when the pattern must be
+// replaced by the fallback draw, -1 when a row index was outside [0, m); ocor[p]: the orientation
+// correlation after the flip (NaN where none was taken)
+size_t collapse_ws_doubles(long long k, int ncells, int pick_top);
+hipError_t launch_collapse(const double* x, const double* w, int ncells, int m, int nclust, const long long* off,
+                           const int* idx, const long long* ws_off, double* ws, int scale, int pick_top, double* d,
+                           double* wo, int* top, int* status, double* ocor, hipStream_t s);
+
 }  // namespace scde
