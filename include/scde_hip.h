@@ -497,6 +497,64 @@ int scde_hclust_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, int m
 int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int* n,
                           int method, int* merge, double* height, int* order);
 
+/* ---------------------------------------------------------------- optimal leaf ordering
+ * cba::order.optimal(dist, merge), the step of pagoda.cluster.cells after hclust
+ * (R/functions.R:2668-2672): among the 2^(n-1) orientations of the tree, the one whose
+ * left-to-right leaf order has the smallest summed distance between neighbours (Bar-Joseph,
+ * Gifford and Jaakkola 2001), on the device (csrc/olo.hip: min-plus products level by level, the
+ * choice walked top-down by one workgroup).
+ *
+ * Input.  n >= 2 objects; d: n x n doubles, column-major, ld >= n.  Only the strict lower
+ * triangle is read, and every value read must be finite: otherwise SCDE_EARG naming the first
+ * offending pair in column-major order.  merge: (n - 1) x 2 ints, column-major, R's encoding
+ * (negative: an observation; positive: an earlier step).  Row s defines node s with left child L
+ * (column 1) and right child R (column 2).  A merge matrix that is no tree over all n
+ * observations -- an observation missing or used twice, a step used before it exists, used twice
+ * or referring to itself -- is SCDE_EARG naming the row.  The merge matrix (and a host d) are
+ * checked on the host before anything is allocated.  The caller's matrices are never written.
+ *
+ * The table.  p(x): the position of observation x in the input tree's own left-to-right leaf
+ * order (recomputed from merge; hclust's order for an hclust result).  M(x, x) = 0, and for a
+ * node v with children L, R and every u in L, w in R
+ *   M(u, w) = M(w, u) = min over m in far(L, u), k in far(R, w) of
+ *                       fl( fl( M(u, m) + d(m, k) ) + M(k, w) )
+ * with far(c, x) = {x} for a leaf c, otherwise the leaves of the child of c that does not
+ * contain x.  The association is always the L term first, then d, then the R term, whatever
+ * orientation is chosen in the end; float64, no contraction; min is numeric (-0.0 ties with
+ * 0.0).  Rounded addition is monotone, so the two-step form
+ *   T(u, k) = min_m fl( M(u, m) + d(m, k) ),   M(u, w) = min_k fl( T(u, k) + M(k, w) )
+ * and any tiling or reduction order give the same bits.
+ *
+ * The choice, top-down.  The root is never flipped (the reversal of the whole order is not
+ * looked at).  Its end points are the lexicographic minimum of (M(u, w), p(u), p(w)), u in
+ * L_root, w in R_root.  At a node v whose end points are a in L and b in R -- whichever of the
+ * two is the left one -- the joint (m, k) is the lexicographic minimum of
+ * (fl( fl( M(a, m) + d(m, k) ) + M(k, b) ), p(m), p(k)) over m in far(L, a), k in far(R, b),
+ * always evaluated in this forward form; its cost equals M(a, b) bit for bit.  L continues with
+ * the end points (a, m), R with (k, b); v is flipped when its left-most end point lies in R.
+ *
+ * Outputs (host).
+ *   merge_out  merge with the two columns of every flipped row swapped and nothing else changed
+ *              (cba's convention; hclust's singleton-first rule no longer holds for such a row)
+ *   order_out  n ints, 1-based: the leaves of merge_out left to right
+ *   length     (may be NULL) d summed along order_out, left to right, in float64
+ * n = 2 returns the input.  merge_out and order_out may not alias merge or each other
+ * (SCDE_EARG).
+ *
+ * Which of several equally short orders cba itself returns is unknown: the tie rule above is
+ * this library's own, and nothing here was checked against a run of R or cba.
+ *
+ * SCDE_EHIP with an "out of memory" message, before any launch, when the workspace (3 n^2 + O(n)
+ * doubles: M, T and d in leaf order) cannot be allocated; it is freed before the call returns.
+ * Statistics "olo_launches" and "olo_candidates" (one float64 add and one min each) describe
+ * the context's last call.  ctx may be NULL. */
+int scde_order_optimal_host(scde_ctx* ctx, const double* d, int64_t ld, int n, const int* merge, int* merge_out,
+                            int* order_out, double* length);
+/* d_dev is resident in HBM and is left unmodified (its values are checked by a kernel); merge is
+ * a host array; results go to the host. */
+int scde_order_optimal_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, const int* merge, int* merge_out,
+                           int* order_out, double* length);
+
 /* 1 - cor(x) of the columns of a resident nrow x ncol column-major matrix (the correlation of
  * scde_matCorr), written to the resident ncol x ncol matrix out_dev, both triangles, the
  * diagonal exactly 0 (as.matrix(as.dist(.))): pagoda.gene.clusters' gene-to-gene distance, ready

@@ -11,8 +11,9 @@ from .api import (Context, DeviceCounts, RatioPosterior, ScdeError, bh_cz, calcu
                   scde_posteriors, set_rand)
 from .aspects import (collapse_aspect_clusters, pagoda_reduce_loading_redundancy,  # noqa: F401
                       pagoda_reduce_redundancy, pathway_pc_correlation_distance)
-from .cluster import (HClust, cutree, hclust, hclust_batch, pagoda_cluster_cells,  # noqa: F401
-                      pagoda_gene_cluster_samples, pagoda_gene_clusters, pagoda_gene_clusters_observed)
+from .cluster import (HClust, cutree, hclust, hclust_batch, leaf_order_length, order_optimal,  # noqa: F401
+                      pagoda_cluster_cells, pagoda_gene_cluster_samples, pagoda_gene_clusters,
+                      pagoda_gene_clusters_observed)
 from .distance import (direct_dropout_distance, mode_relative_distance, reciprocal_distance,  # noqa: F401
                        weighted_correlation)
 from .prior import expression_prior  # noqa: F401

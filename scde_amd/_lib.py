@@ -34,6 +34,7 @@ EXPORTS = [
     "scde_gather_cols_dev", "scde_sigma1sq_batch_dev", "scde_dev_mem_info",
     "scde_plSemicompleteCor2_dev", "scde_t_renorm_dev", "scde_t_renorm_host", "scde_aspect_distance_dev",
     "scde_matWCorr_distance_dev", "scde_collapse_aspects_dev",
+    "scde_order_optimal_host", "scde_order_optimal_dev",
 ]
 
 
@@ -138,6 +139,7 @@ def lib():
                                                                          ctypes.c_uint64, P]
     L.scde_hclust_host.argtypes = L.scde_hclust_dev.argtypes = [P, P, i64, i, i, P, P, P]
     L.scde_hclust_batch_dev.argtypes = [P, i, P, P, P, i, P, P, P]
+    L.scde_order_optimal_host.argtypes = L.scde_order_optimal_dev.argtypes = [P, P, i64, i, P, P, P, P]
     L.scde_cor_distance_dev.argtypes = [P, P, i, i, P]
     L.scde_r_norm_rand.argtypes = L.scde_r_mt_words.argtypes = [P, i64, P]
     L.scde_rnorm_matrix_dev.argtypes = [P, P, i, i, P]

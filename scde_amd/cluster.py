@@ -5,6 +5,9 @@ PAGODA steps that consume a distance matrix.
                                            complete, average, mcquitty (merge, height, order in
                                            R's encoding)
   * ``cutree``                             R's ``cutree`` (numpy; O(n) per cut)
+  * ``order_optimal`` / ``leaf_order_length``  ``cba::order.optimal``: the orientation of a tree
+                                           whose leaf order has the smallest summed distance
+                                           between neighbours (csrc/olo.hip)
   * ``pagoda_cluster_cells``               R/functions.R:2641-2678
   * ``pagoda_gene_clusters_observed``      R/functions.R:2060-2121, the observed half of
                                            ``pagoda.gene.clusters``
@@ -115,6 +118,50 @@ def hclust_batch(ds, method="ward.D", ctx: api.Context | None = None):
     return out
 
 
+def _order_optimal(ctx, d, ld, n, merge, dev):
+    """The C entry on a host array (``d``: an ndarray) or a resident matrix (``d``: a pointer)."""
+    merge = np.asfortranarray(merge, dtype=np.int32)
+    if merge.shape != (n - 1, 2):
+        raise ValueError(f"merge must be {n - 1} x 2 for {n} objects")
+    merge_out = np.zeros((n - 1, 2), np.int32, order="F")
+    order = np.zeros(n, np.int32)
+    length = ctypes.c_double()
+    f = lib().scde_order_optimal_dev if dev else lib().scde_order_optimal_host
+    check(f(ctx.handle if ctx else None, d if dev else api._p(d), ld, n, api._p(merge), api._p(merge_out),
+            api._p(order), ctypes.byref(length)))
+    return merge_out, order, length.value
+
+
+def order_optimal(hc, d, ctx: api.Context | None = None, return_length=False):
+    """``cba::order.optimal(as.dist(d), hc$merge)``: ``hc`` (an ``HClust`` or anything with
+    ``.merge``) re-oriented so that the summed distance between neighbouring leaves is the
+    smallest of all 2^(n - 1) orientations (Bar-Joseph, Gifford and Jaakkola 2001; the contract is
+    in include/scde_hip.h).  ``d`` as for ``hclust``.  Returns a new ``HClust``: ``merge`` with
+    the columns of the flipped rows swapped (cba's convention), ``order`` its leaves left to
+    right, ``height``, ``method`` and ``labels`` kept; with ``return_length`` also the path length
+    (``leaf_order_length(d, order)``).
+
+    The root is never flipped, and among equally short orders the (cost, position, position)
+    rule of the header decides.  Which of them cba itself returns is unknown, and nothing here was
+    checked against a run of R or cba."""
+    a, _ = _square(d)
+    merge_out, order, length = _order_optimal(ctx, a, a.shape[0], a.shape[0], hc.merge, dev=False)
+    out = HClust(merge_out, getattr(hc, "height", None), order, getattr(hc, "method", None),
+                 getattr(hc, "labels", None))
+    return (out, length) if return_length else out
+
+
+def leaf_order_length(d, order):
+    """The summed distance between neighbours of ``order`` (1-based), added left to right in
+    float64; ``d`` is read in its lower triangle."""
+    a = np.asarray(d.values if hasattr(d, "index") and hasattr(d, "columns") else d, dtype=np.float64)
+    o = np.asarray(order, dtype=np.int64) - 1
+    total = 0.0
+    for v in a[np.maximum(o[:-1], o[1:]), np.minimum(o[:-1], o[1:])].tolist():
+        total += v
+    return total
+
+
 def cutree(hc, k=None, h=None):
     """R's ``cutree``: 1-based labels per observation, clusters numbered by the first
     observation they contain.  ``k`` clusters are the state after n - k steps; a height ``h``
@@ -152,14 +199,17 @@ def cutree(hc, k=None, h=None):
 
 
 def pagoda_cluster_cells(tam, varinfo, method="ward.D", include_aspects=False, return_details=False,
-                         min_overdispersion=1, ctx: api.Context | None = None):
+                         min_overdispersion=1, ctx: api.Context | None = None, optimal_order=False):
     """R/functions.R:2641-2678.  ``tam``: {"gw": {gene: weight} (or a Series), and with
     ``include_aspects`` "xv", "xvw": aspects x cells}; ``varinfo``: the dict
     ``pagoda_pathway_wPCA`` takes (mat, matw genes x cells; genes; optionally "cells") plus
     "arv" (per gene).  Genes of ``gw`` with rowSums(matw) * arv > min_overdispersion are kept,
-    the cells' weighted correlation is ``matWCorr`` and the tree is ``hclust(1 - dm)``.  The
-    optional ``cba`` leaf reordering is not restated.  With ``return_details``: {"clustering",
-    "distance" (lower triangle as matWCorr fills it), "genes"}."""
+    the cells' weighted correlation is ``matWCorr`` and the tree is ``hclust(1 - dm)``.  With
+    ``optimal_order`` the tree is then re-oriented by ``order_optimal`` on the same distance, as
+    the reference does when ``cba`` is installed (R/functions.R:2668-2672: ``merge`` and ``order``
+    replaced); the matrix is uploaded once and stays in HBM between the two steps.  The default
+    leaves hclust's own order.  With ``return_details``: {"clustering", "distance" (lower triangle
+    as matWCorr fills it), "genes"}."""
     from .pagoda import matWCorr
     _method_code(method)
     mat = np.asarray(varinfo["mat"], dtype=np.float64)
@@ -182,7 +232,21 @@ def pagoda_cluster_cells(tam, varinfo, method="ward.D", include_aspects=False, r
         wgm = np.vstack([wgm, np.asarray(tam["xv"], dtype=np.float64)])
         wgwm = np.vstack([wgwm, np.asarray(tam["xvw"], dtype=np.float64)])
     dm = 1.0 - matWCorr(wgm, wgwm)
-    hc = hclust(dm, method=method, ctx=ctx)
+    if optimal_order:
+        ctx = ctx or api.default_context()
+        a, _ = _square(dm)
+        n = a.shape[0]
+        L = lib()
+        ptr = ctypes.c_void_p()
+        check(L.scde_dev_alloc(ctx.handle, a.nbytes, ctypes.byref(ptr)))
+        try:
+            check(L.scde_h2d(ctx.handle, ptr, api._p(a), a.nbytes))
+            hc = _hclust_dev(ctx, ptr, n, method)
+            hc.merge, hc.order, _ = _order_optimal(ctx, ptr, n, n, hc.merge, dev=True)
+        finally:
+            check(L.scde_dev_free(ctx.handle, ptr))
+    else:
+        hc = hclust(dm, method=method, ctx=ctx)
     cells = varinfo.get("cells")
     hc.labels = [str(c) for c in cells] if cells is not None else None
     if return_details:

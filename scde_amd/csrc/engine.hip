@@ -413,6 +413,7 @@ struct scde_ctx {
   // run_posterior's pieces (host ms): waiting for a piece's upload, then its unique build and tables launch
   double st_piece_wait_ms = 0, st_piece_host_ms = 0;
   double st_pair_redo = 0;  // slabs the gene blocks left to the four-tile list pass (k_boot_tiles)
+  double st_olo[2] = {0, 0};  // the last optimal leaf ordering: kernel launches, candidates (add + min each)
   double st_boot_path = -1;  // the bootstrap kernel of the last posterior: 0 k_boot2, 1 k_boot_tiles, 3 general
   static constexpr int kQMaxTilesHost = 28;
   double st_tile_hist[kQMaxTilesHost + 1] = {0};
@@ -2066,6 +2067,8 @@ int scde_ctx_get_stat(scde_ctx* ctx, const char* name, double* value) {
   else if (n == "skip_redo") *value = ctx->st_skip_redo;
   else if (n == "pair_redo") *value = ctx->st_pair_redo;
   else if (n == "degen") *value = ctx->st_degen;
+  else if (n == "olo_launches") *value = ctx->st_olo[0];
+  else if (n == "olo_candidates") *value = ctx->st_olo[1];
   else if (n == "stream_syncs") *value = ctx->st_stream_syncs + (ctx->peer ? ctx->peer->st_stream_syncs : 0);
   else if (n == "arena_syncs") *value = ctx->st_arena_syncs + (ctx->peer ? ctx->peer->st_arena_syncs : 0);
   else if (n == "piece_wait_ms") *value = ctx->st_piece_wait_ms + (ctx->peer ? ctx->peer->st_piece_wait_ms : 0);
@@ -4585,6 +4588,65 @@ int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const i
     ldv[p] = n[p];
   }
   return hclust_run(ctx, nprob, d_dev, off, ldv.data(), n, method, merge, height, order);
+}
+
+// ------------------------------------------------------------------ optimal leaf ordering
+// cba::order.optimal (olo.hip; contract in scde_hip.h).  The arguments and the merge matrix are
+// checked on the host before the GPU is touched.
+static int olo_check(const void* d, int64_t ld, int n, const int* merge, const int* merge_out, const int* order_out) {
+  if (!d || !merge || !merge_out || !order_out) return fail(SCDE_EARG, "null argument");
+  if (n < 2) return fail(SCDE_EARG, "order.optimal: at least 2 objects are needed (n = %d)", n);
+  if (ld < n) return fail(SCDE_EARG, "order.optimal: ld must be at least n");
+  const uintptr_t mb = (uintptr_t)merge, mob = (uintptr_t)merge_out, oob = (uintptr_t)order_out;
+  const uintptr_t me = mb + sizeof(int) * 2 * (size_t)(n - 1), moe = mob + sizeof(int) * 2 * (size_t)(n - 1),
+                  ooe = oob + sizeof(int) * (size_t)n;
+  if ((mob < me && mb < moe) || (oob < me && mb < ooe) || (oob < moe && mob < ooe))
+    return fail(SCDE_EARG, "order.optimal: merge_out and order_out must not alias merge or each other");
+  char msg[256];
+  if (olo_check_merge(n, merge, msg, sizeof(msg))) return fail(SCDE_EARG, "%s", msg);
+  return SCDE_OK;
+}
+
+static int olo_run(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, const int* merge, int* merge_out,
+                   int* order_out, double* length) {
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = olo_solve(ctx->stream, d_dev, ld, n, merge, merge_out, order_out, length, ctx->st_olo, msg,
+                           sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  RCHK(ctx->sync());
+  if (rc) return fail(rc == 1 ? SCDE_EARG : rc == 2 ? SCDE_EHIP : SCDE_EINTERNAL, "%s", msg);
+  return SCDE_OK;
+}
+
+int scde_order_optimal_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, const int* merge, int* merge_out,
+                           int* order_out, double* length) {
+  FORK_GUARD();
+  RCHK(olo_check(d_dev, ld, n, merge, merge_out, order_out));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  return olo_run(ctx, d_dev, ld, n, merge, merge_out, order_out, length);
+}
+
+int scde_order_optimal_host(scde_ctx* ctx, const double* d, int64_t ld, int n, const int* merge, int* merge_out,
+                            int* order_out, double* length) {
+  FORK_GUARD();
+  RCHK(olo_check(d, ld, n, merge, merge_out, order_out));
+  for (int j = 0; j < n - 1; ++j)
+    for (int i = j + 1; i < n; ++i)
+      if (!std::isfinite(d[i + (size_t)j * ld]))
+        return fail(SCDE_EARG, "order.optimal: non-finite distance at row %d, column %d (1-based)", i + 1, j + 1);
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  if (ctx->hc_in.ensure(sizeof(double) * (size_t)n * n) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "order.optimal: out of memory: the matrix needs %zu bytes of device memory",
+                sizeof(double) * (size_t)n * n);
+  }
+  RCHK(dist_put(ctx, ctx->hc_in, d, ld, n, n));
+  const int rc = olo_run(ctx, ctx->hc_in.as<double>(), n, n, merge, merge_out, order_out, length);
+  if (sizeof(double) * (size_t)n * n > ((size_t)1 << 30)) ctx->hc_in.release();
+  return rc;
 }
 
 // 1 - cor of the columns of a resident nrow x ncol matrix, into a resident ncol x ncol matrix

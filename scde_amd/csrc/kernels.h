@@ -443,6 +443,17 @@ hipError_t launch_one_minus(double* x, long long n, hipStream_t s);
 void hclust_encode(int n, const int* si, const int* sj, const double* sh, int method, int* merge, double* height,
                    int* order);
 
+// ---- optimal leaf ordering (olo.hip; the contract is in include/scde_hip.h).
+// 0, or the 1-based row that makes merge ((n - 1) x 2, R's encoding) no tree over n observations;
+// msg says why (host)
+int olo_check_merge(int n, const int* merge, char* msg, size_t cap);
+// The whole computation on a resident n x n matrix (strict lower triangle read) and a checked
+// merge: workspace (3 n^2 doubles + O(n)) allocated and freed inside, results to the host.
+// 0 done; 1 an argument error (a non-finite distance); 2 a HIP error (out of memory included);
+// 3 an internal error; msg holds the text.  stats (may be null): launches, candidates.
+int olo_solve(hipStream_t s, const double* d_dev, long long ld, int n, const int* merge, int* merge_out,
+              int* order_out, double* length, double* stats, char* msg, size_t cap);
+
 // ---- the randomised rounds of pagoda.gene.clusters (rnorm.hip, pagoda.hip, sigma1.hip; contract
 // in include/scde_hip.h).  Round matrices are ncells x ngenes column-major (a gene contiguous).
 // R's norm_rand() (INVERSION) from raw Mersenne-Twister outputs, two per normal: draw t goes to
