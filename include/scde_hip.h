@@ -561,6 +561,87 @@ int scde_order_optimal_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n
  * for scde_hclust_dev. */
 int scde_cor_distance_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev);
 
+/* ---------------------------------------------------------------- exact t-SNE of a distance matrix
+ * The 2-D embedding the PAGODA walkthrough draws from pagoda.cluster.cells' distance
+ * (vignettes/pagoda.md:230-250: Rtsne(cell.clustering$distance, is_distance = TRUE,
+ * perplexity = 10)); csrc/tsne.hip.  This is van der Maaten's exact t-SNE, the method that
+ * Rtsne(theta = 0) wraps, written from the published algorithm (van der Maaten and Hinton 2008;
+ * the gradient in bhtsne's form).  The vignette's call uses Rtsne's default Barnes-Hut
+ * approximation (theta = 0.5), of which this is the exact limit; Barnes-Hut is not built.
+ * Nothing here was checked against a run of Rtsne: Rtsne is not available to this project.
+ *
+ * Input.  d: n x n doubles, column-major, leading dimension ld >= n.  Only the strict lower
+ * triangle is read (as scde_hclust_* read it; scde_matWCorr's half-filled matrix is accepted as
+ * is): delta_ij = d[max(i, j) + min(i, j) ld].  D2_ij = delta_ij^2, or delta_ij itself with
+ * squared != 0.  Whether Rtsne squares a precomputed distance in its exact mode is not known
+ * here.  A NaN, an infinity or a negative value in the strict lower triangle (also a value whose
+ * square overflows) is SCDE_EARG, the message naming the first such pair in column-major order,
+ * before any iteration.  n >= 4, perplexity >= 1 and 3 perplexity <= n - 1 (Rtsne's rule), else
+ * SCDE_EARG.
+ *
+ * Affinities, for every row i over j != i.  beta = 1, lo = -inf, hi = +inf; up to 200 evaluations
+ *   p_j = exp(-beta D2_ij),  s = sum_j p_j + DBL_MIN,  H = beta (sum_j D2_ij p_j) / s + log s,
+ *   delta = H - log(perplexity)
+ * stopping when |delta| < 1e-5; otherwise, delta > 0: lo = beta, beta = 2 beta while hi is
+ * infinite, else (beta + hi) / 2; delta <= 0: hi = beta, beta = beta / 2 while lo is infinite,
+ * else (beta + lo) / 2.  The row keeps p_{j|i} = p_j / s of the last beta it evaluated, and that
+ * beta is reported; p_{i|i} = 0.  Then P_ij = (p_{j|i} + p_{i|j}) / (2 n), the paper's form: P
+ * is symmetric bit for bit, its diagonal is 0 and it sums to 1 without a global sum.
+ *
+ * Iteration t = 0 .. max_iter - 1 on the state Y, uY (zeros at t = 0), gains (ones at t = 0),
+ * each n x 2.  ex = exaggeration while t <= stop_lying_iter and 1 after it (P itself is never
+ * scaled); mom = momentum while t <= mom_switch_iter, final_momentum after it.  With
+ * Q_ij = 1 / (1 + |Y_i - Y_j|^2), for every i over j != i
+ *   A_i = sum_j ex P_ij Q_ij (Y_i - Y_j),  R_i = sum_j Q_ij^2 (Y_i - Y_j),  S_i = sum_j Q_ij,
+ *   sumQ = sum_i S_i,  dY_i = A_i - R_i / sumQ
+ * (bhtsne's (P - Q / sumQ) Q form, split so that one pass over P serves an iteration; no factor
+ * 4, as in bhtsne).  Per coordinate, with sign(0) = 0:
+ *   gain = gain + 0.2 if sign(dY) != sign(uY), else gain * 0.8;  gain = max(gain, 0.01);
+ *   uY = mom uY - eta gain dY;  Y = Y + uY
+ * and then each column of Y has its mean (column sum / n) subtracted.  Rtsne's defaults:
+ * perplexity 30, max_iter 1000, eta 200, exaggeration 12, stop_lying_iter 250,
+ * mom_switch_iter 250, momentum 0.5, final_momentum 0.8.
+ *
+ * Cost.  costs[i] = sum_{j != i} P_ij log((P_ij + FLT_MIN) / (Q_ij / sumQ + FLT_MIN)),
+ * FLT_MIN = 2^-126; the sum of costs is the Kullback-Leibler divergence.
+ *
+ * Initial Y.  The caller's n x 2 matrix, or Y0[i, c] = 1e-4 z[2 i + c] with z the first 2 n
+ * values of scde_r_norm_rand after scde_r_set_seed(seed) (R's rnorm after set.seed).  Rtsne's own
+ * generator is not known here: the seeded start is this library's choice.
+ *
+ * Layout.  Y, uY, gains and Y_init are n x 2 row-major (a point's two coordinates adjacent);
+ * resident ones must be 16-byte aligned.  P is n x n, both triangles.  beta and costs are host
+ * arrays of n.
+ *
+ * Determinism.  No floating-point atomics; every sum is taken in an order that depends on n
+ * alone (Q's reciprocal is the hardware estimate refined by one Newton step).  Results repeat bit
+ * for bit from run to run, the host and device entries agree bit for bit, and a run split at any
+ * iteration and resumed from (Y, uY, gains, iter0) equals the unsplit run bit for bit.
+ *
+ * ctx may be NULL.  The device entries take a workspace of scde_tsne_ws_bytes(n) bytes (resident,
+ * 8-byte aligned; O(n^2 / 64 + n) doubles); a missing, smaller or misaligned one is SCDE_EARG.  Argument errors leave P and
+ * the state untouched; a refused distance leaves the contents of P_dev undefined. */
+int scde_tsne_ws_bytes(int n, int64_t* bytes);
+/* d_dev resident (left unmodified), P_dev resident n x n (must not overlap d_dev), beta host. */
+int scde_tsne_affinities_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, double perplexity, int squared,
+                             double* P_dev, double* beta, void* ws_dev, int64_t ws_bytes);
+/* Iterations iter0 .. iter0 + niter - 1 on the resident state, in place; niter = 0 does nothing. */
+int scde_tsne_iterate_dev(scde_ctx* ctx, const double* P_dev, int n, double eta, double exaggeration,
+                          int stop_lying_iter, int mom_switch_iter, double momentum, double final_momentum,
+                          int iter0, int niter, double* Y_dev, double* uY_dev, double* gains_dev, void* ws_dev,
+                          int64_t ws_bytes);
+int scde_tsne_cost_dev(scde_ctx* ctx, const double* P_dev, int n, const double* Y_dev, double* costs, void* ws_dev,
+                       int64_t ws_bytes);
+/* Upload, affinities, max_iter iterations and the cost in one call, everything on the host side:
+ * Y_init may be NULL (the seeded start) and may be Y; P (n x n, may be NULL) receives the
+ * affinities.  max_iter = 0 returns the initial Y and its cost.  SCDE_EHIP with an "out of memory"
+ * message, before any launch, when the 2 n^2 doubles and the workspace cannot be allocated; they
+ * are freed before the call returns. */
+int scde_tsne_host(scde_ctx* ctx, const double* d, int64_t ld, int n, double perplexity, int squared, double eta,
+                   double exaggeration, int stop_lying_iter, int mom_switch_iter, double momentum,
+                   double final_momentum, int max_iter, uint32_t seed, const double* Y_init, double* Y, double* costs,
+                   double* beta, double* P);
+
 /* ---------------------------------------------------------------- pagoda.gene.clusters' random rounds
  * The null model of pagoda.gene.clusters (R/functions.R:2131-2192): per round i, set.seed(i), a
  * genes x cells matrix of rnorm, winsorize, drop the genes that fail the keep rule, 1 - cor,

@@ -16,6 +16,7 @@ from .cluster import (HClust, cutree, hclust, hclust_batch, leaf_order_length, o
                       pagoda_gene_clusters_observed)
 from .distance import (direct_dropout_distance, mode_relative_distance, reciprocal_distance,  # noqa: F401
                        weighted_correlation)
+from .embedding import TsneState, tsne_affinities, tsne_embedding, tsne_iterate  # noqa: F401
 from .prior import expression_prior  # noqa: F401
 
 __version__ = "0.1.0"

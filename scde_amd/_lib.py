@@ -35,6 +35,7 @@ EXPORTS = [
     "scde_plSemicompleteCor2_dev", "scde_t_renorm_dev", "scde_t_renorm_host", "scde_aspect_distance_dev",
     "scde_matWCorr_distance_dev", "scde_collapse_aspects_dev",
     "scde_order_optimal_host", "scde_order_optimal_dev",
+    "scde_tsne_ws_bytes", "scde_tsne_affinities_dev", "scde_tsne_iterate_dev", "scde_tsne_cost_dev", "scde_tsne_host",
 ]
 
 
@@ -140,6 +141,11 @@ def lib():
     L.scde_hclust_host.argtypes = L.scde_hclust_dev.argtypes = [P, P, i64, i, i, P, P, P]
     L.scde_hclust_batch_dev.argtypes = [P, i, P, P, P, i, P, P, P]
     L.scde_order_optimal_host.argtypes = L.scde_order_optimal_dev.argtypes = [P, P, i64, i, P, P, P, P]
+    L.scde_tsne_ws_bytes.argtypes = [i, P]
+    L.scde_tsne_affinities_dev.argtypes = [P, P, i64, i, d, i, P, P, P, i64]
+    L.scde_tsne_iterate_dev.argtypes = [P, P, i, d, d, i, i, d, d, i, i, P, P, P, P, i64]
+    L.scde_tsne_cost_dev.argtypes = [P, P, i, P, P, P, i64]
+    L.scde_tsne_host.argtypes = [P, P, i64, i, d, i, d, d, i, i, d, d, i, ctypes.c_uint32, P, P, P, P, P]
     L.scde_cor_distance_dev.argtypes = [P, P, i, i, P]
     L.scde_r_norm_rand.argtypes = L.scde_r_mt_words.argtypes = [P, i64, P]
     L.scde_rnorm_matrix_dev.argtypes = [P, P, i, i, P]

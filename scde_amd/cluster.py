@@ -209,7 +209,8 @@ def pagoda_cluster_cells(tam, varinfo, method="ward.D", include_aspects=False, r
     the reference does when ``cba`` is installed (R/functions.R:2668-2672: ``merge`` and ``order``
     replaced); the matrix is uploaded once and stays in HBM between the two steps.  The default
     leaves hclust's own order.  With ``return_details``: {"clustering", "distance" (lower triangle
-    as matWCorr fills it), "genes"}."""
+    as matWCorr fills it), "genes"}.  The walkthrough's 2-D embedding of the cells is
+    ``tsne_embedding(details["distance"], perplexity=10)`` (``scde_amd/embedding.py``)."""
     from .pagoda import matWCorr
     _method_code(method)
     mat = np.asarray(varinfo["mat"], dtype=np.float64)

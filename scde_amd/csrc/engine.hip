@@ -4649,6 +4649,172 @@ int scde_order_optimal_host(scde_ctx* ctx, const double* d, int64_t ld, int n, c
   return rc;
 }
 
+// ------------------------------------------------------------------ exact t-SNE
+// The 2-D embedding of a distance matrix (tsne.hip; contract in scde_hip.h).  Arguments are
+// checked before the GPU is touched.
+static int tsne_check_n(int n) {
+  if (n < 4) return fail(SCDE_EARG, "tsne: at least 4 objects are needed (n = %d)", n);
+  return SCDE_OK;
+}
+
+static int tsne_check_perplexity(int n, double perplexity) {
+  RCHK(tsne_check_n(n));
+  if (!(perplexity >= 1.0) || !(3.0 * perplexity <= (double)(n - 1)))
+    return fail(SCDE_EARG, "tsne: perplexity must be at least 1 and 3 * perplexity at most n - 1 (perplexity = %g, "
+                "n = %d)", perplexity, n);
+  return SCDE_OK;
+}
+
+static int tsne_check_params(const TsneParams& p, int iter0, int niter) {
+  if (!std::isfinite(p.eta) || !std::isfinite(p.exaggeration) || !std::isfinite(p.momentum) ||
+      !std::isfinite(p.final_momentum))
+    return fail(SCDE_EARG, "tsne: eta, exaggeration, momentum and final_momentum must be finite");
+  if (iter0 < 0 || niter < 0) return fail(SCDE_EARG, "tsne: iter0 and the number of iterations must not be negative");
+  return SCDE_OK;
+}
+
+static int tsne_check_ws(int n, const void* ws, int64_t ws_bytes) {
+  if (!ws || ws_bytes < (int64_t)tsne_ws_bytes(n))
+    return fail(SCDE_EARG, "tsne: the workspace is missing or too small (%lld bytes given, scde_tsne_ws_bytes(%d) = "
+                "%zu)", ws ? (long long)ws_bytes : 0ll, n, tsne_ws_bytes(n));
+  if ((uintptr_t)ws & 7) return fail(SCDE_EARG, "tsne: the workspace must be 8-byte aligned");
+  return SCDE_OK;
+}
+
+static int tsne_rc(int rc, const char* msg) {
+  return rc ? fail(rc == 1 ? SCDE_EARG : SCDE_EHIP, "%s", msg) : SCDE_OK;
+}
+
+int scde_tsne_ws_bytes(int n, int64_t* bytes) {
+  if (!bytes) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_n(n));
+  *bytes = (int64_t)tsne_ws_bytes(n);
+  return SCDE_OK;
+}
+
+int scde_tsne_affinities_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, double perplexity, int squared,
+                             double* P_dev, double* beta, void* ws_dev, int64_t ws_bytes) {
+  FORK_GUARD();
+  if (!d_dev || !P_dev || !beta) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_perplexity(n, perplexity));
+  if (ld < n) return fail(SCDE_EARG, "tsne: ld must be at least n");
+  RCHK(tsne_check_ws(n, ws_dev, ws_bytes));
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = tsne_affinities(ctx->stream, d_dev, ld, n, perplexity, squared, P_dev, beta,
+                                 static_cast<char*>(ws_dev), msg, sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return tsne_rc(rc, msg);
+}
+
+int scde_tsne_iterate_dev(scde_ctx* ctx, const double* P_dev, int n, double eta, double exaggeration,
+                          int stop_lying_iter, int mom_switch_iter, double momentum, double final_momentum,
+                          int iter0, int niter, double* Y_dev, double* uY_dev, double* gains_dev, void* ws_dev,
+                          int64_t ws_bytes) {
+  FORK_GUARD();
+  if (!P_dev || !Y_dev || !uY_dev || !gains_dev) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_n(n));
+  const TsneParams prm = {eta, exaggeration, momentum, final_momentum, stop_lying_iter, mom_switch_iter};
+  RCHK(tsne_check_params(prm, iter0, niter));
+  RCHK(tsne_check_ws(n, ws_dev, ws_bytes));
+  if (((uintptr_t)Y_dev | (uintptr_t)uY_dev | (uintptr_t)gains_dev) & 15)
+    return fail(SCDE_EARG, "tsne: Y, uY and gains must be 16-byte aligned");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = tsne_iterate(ctx->stream, P_dev, n, prm, iter0, niter, Y_dev, uY_dev, gains_dev,
+                              static_cast<char*>(ws_dev), msg, sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return tsne_rc(rc, msg);
+}
+
+int scde_tsne_cost_dev(scde_ctx* ctx, const double* P_dev, int n, const double* Y_dev, double* costs, void* ws_dev,
+                       int64_t ws_bytes) {
+  FORK_GUARD();
+  if (!P_dev || !Y_dev || !costs) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_n(n));
+  RCHK(tsne_check_ws(n, ws_dev, ws_bytes));
+  if ((uintptr_t)Y_dev & 15) return fail(SCDE_EARG, "tsne: Y must be 16-byte aligned");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = tsne_cost(ctx->stream, P_dev, n, Y_dev, costs, static_cast<char*>(ws_dev), msg, sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return tsne_rc(rc, msg);
+}
+
+int scde_tsne_host(scde_ctx* ctx, const double* d, int64_t ld, int n, double perplexity, int squared, double eta,
+                   double exaggeration, int stop_lying_iter, int mom_switch_iter, double momentum,
+                   double final_momentum, int max_iter, uint32_t seed, const double* Y_init, double* Y, double* costs,
+                   double* beta, double* P) {
+  FORK_GUARD();
+  if (!d || !Y || !costs || !beta) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_perplexity(n, perplexity));
+  if (ld < n) return fail(SCDE_EARG, "tsne: ld must be at least n");
+  const TsneParams prm = {eta, exaggeration, momentum, final_momentum, stop_lying_iter, mom_switch_iter};
+  RCHK(tsne_check_params(prm, 0, max_iter));
+  const size_t nn = (size_t)n;
+  std::vector<double> y0(2 * nn);
+  if (Y_init) {
+    std::copy(Y_init, Y_init + 2 * nn, y0.begin());
+  } else {  // 1e-4 * rnorm(2 n) after set.seed(seed), point by point
+    uint32_t state[625];
+    RCHK(scde_r_set_seed(seed, state));
+    RCHK(scde_r_norm_rand(state, (int64_t)(2 * nn), y0.data()));
+    for (double& v : y0) v = 1e-4 * v;
+  }
+  if (!ctx) RCHK(default_ctx(&ctx));
+  HCHK(hipSetDevice(ctx->device));
+  // d, P; then Y, uY, gains; then the workspace: one allocation, freed before the call returns
+  const size_t mat = (sizeof(double) * nn * nn + 255) / 256 * 256, vec = (16 * nn + 255) / 256 * 256;
+  const size_t total = 2 * mat + 3 * vec + tsne_ws_bytes(n);
+  char* base = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&base), total) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "tsne: out of memory: %d objects need %zu bytes of device memory", n, total);
+  }
+  double *dd = reinterpret_cast<double*>(base), *Pd = reinterpret_cast<double*>(base + mat),
+         *Yd = reinterpret_cast<double*>(base + 2 * mat), *Ud = reinterpret_cast<double*>(base + 2 * mat + vec),
+         *Gd = reinterpret_cast<double*>(base + 2 * mat + 2 * vec);
+  char* ws = base + 2 * mat + 3 * vec;
+  char msg[256] = "";
+  hipStream_t st = ctx->stream;
+  std::vector<double> ones(2 * nn, 1.0);
+  int rc = 0;
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  do {
+    const size_t row = sizeof(double) * nn;
+    if (!ok(ld == n ? hipMemcpyAsync(dd, d, row * nn, hipMemcpyHostToDevice, st)
+                    : hipMemcpy2DAsync(dd, row, d, sizeof(double) * (size_t)ld, row, nn, hipMemcpyHostToDevice, st)))
+      break;
+    if (!ok(hipMemcpyAsync(Yd, y0.data(), 16 * nn, hipMemcpyHostToDevice, st))) break;
+    if (!ok(hipMemcpyAsync(Gd, ones.data(), 16 * nn, hipMemcpyHostToDevice, st))) break;
+    if (!ok(hipMemsetAsync(Ud, 0, 16 * nn, st))) break;
+    if ((rc = tsne_affinities(st, dd, n, n, perplexity, squared, Pd, beta, ws, msg, sizeof(msg)))) break;
+    if ((rc = tsne_iterate(st, Pd, n, prm, 0, max_iter, Yd, Ud, Gd, ws, msg, sizeof(msg)))) break;
+    if ((rc = tsne_cost(st, Pd, n, Yd, costs, ws, msg, sizeof(msg)))) break;
+    if (!ok(hipMemcpyAsync(Y, Yd, 16 * nn, hipMemcpyDeviceToHost, st))) break;
+    if (P && !ok(hipMemcpyAsync(P, Pd, sizeof(double) * nn * nn, hipMemcpyDeviceToHost, st))) break;
+    ok(hipStreamSynchronize(st));
+  } while (false);
+  ctx->mark_end(SLOT_OTHER, ev);
+  if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
+  const hipError_t ef = hipFree(base);
+  if (rc) return tsne_rc(rc, msg);
+  if (e != hipSuccess || ef != hipSuccess)
+    return fail(SCDE_EHIP, "tsne: %s", hipGetErrorString(e != hipSuccess ? e : ef));
+  return SCDE_OK;
+}
+
 // 1 - cor of the columns of a resident nrow x ncol matrix, into a resident ncol x ncol matrix
 // (k_matcorr with itself, then 1 - x): pagoda.gene.clusters' distance without a host visit.
 int scde_cor_distance_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev) {

@@ -454,6 +454,28 @@ int olo_check_merge(int n, const int* merge, char* msg, size_t cap);
 int olo_solve(hipStream_t s, const double* d_dev, long long ld, int n, const int* merge, int* merge_out,
               int* order_out, double* length, double* stats, char* msg, size_t cap);
 
+// ---- exact t-SNE of a distance matrix (tsne.hip; the contract is in include/scde_hip.h).
+struct TsneParams {
+  double eta, exaggeration, momentum, final_momentum;
+  int stop_lying_iter, mom_switch_iter;
+};
+// columns per chunk of the gradient kernel and the number of chunks: functions of n alone (they
+// fix the order of every sum)
+int tsne_chunk(int n);
+int tsne_nchunks(int n);
+// bytes of the workspace every call below takes (a multiple of 256)
+size_t tsne_ws_bytes(int n);
+// Each call checks nothing but the data, queues its kernels on s and waits for them.  0 done; 1 an
+// argument error (a refused distance); 2 a HIP error; msg holds the text.  d: n x n column-major,
+// leading dimension ld, strict lower triangle read; P: n x n, receives the affinities (both
+// triangles; it must not overlap d); beta, costs: host, n values; Y, uY, gains: resident, n x 2
+// row-major, 16-byte aligned
+int tsne_affinities(hipStream_t s, const double* d, long long ld, int n, double perplexity, int squared, double* P,
+                    double* beta, char* ws, char* msg, size_t cap);
+int tsne_iterate(hipStream_t s, const double* P, int n, const TsneParams& prm, int iter0, int niter, double* Y,
+                 double* uY, double* gains, char* ws, char* msg, size_t cap);
+int tsne_cost(hipStream_t s, const double* P, int n, const double* Y, double* costs, char* ws, char* msg, size_t cap);
+
 // ---- the randomised rounds of pagoda.gene.clusters (rnorm.hip, pagoda.hip, sigma1.hip; contract
 // in include/scde_hip.h).  Round matrices are ncells x ngenes column-major (a gene contiguous).
 // R's norm_rand() (INVERSION) from raw Mersenne-Twister outputs, two per normal: draw t goes to
