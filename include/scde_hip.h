@@ -302,6 +302,66 @@ int scde_pagoda_varnorm_weights_host(scde_ctx* ctx, const int* counts, int64_t l
                                      const int* batch_codes, int nbatch, int use_expected_value, double* modes,
                                      double* matw, double* bmatw);
 
+/* The weights call above also leaves its modes, matw and bmatw in device memory owned by the
+ * context, for the two stages below; its host outputs matw / bmatw may then be NULL (modes is
+ * always returned).  The context keeps one such set: the next weights call, or a _host entry
+ * below, replaces it.
+ *
+ * pagoda.varnorm, second stage (R/functions.R:1511-1619): per gene g and cell i, at lfpm =
+ * log(avmodes[g]): mu = exp(lfpm corr.a_i + corr.b_i); theta = get.corr.theta (4039-4056: the
+ * five-parameter local form with local_theta, else corr.theta; clamped to [theta_lo, theta_hi],
+ * NaN -> theta_lo); e = (matw[g, i] edf(theta))^weight_df_power; dev = e (count - mu)^2 /
+ * (mu + mu^2 / theta + exp(fail.r_i)).  edf(theta) = exp(S(log theta)), S the natural cubic
+ * spline (linear beyond its ends) of the uniform table: edf_table holds edf_n values at
+ * edf_lt0 + k edf_h, then their edf_n second derivatives (host memory; edf_n >= 2); edf = 1
+ * where theta > 1e3.  A gene with avmodes = 0 is evaluated by IEEE rules, like any other.
+ * out (host), 3 x ngenes: edf = sum e + 1; wvar = sum dev / sum e; rowSums(matw).  With a batch
+ * (batch_codes[ncells] in [0, nbatch), nbatch > 1), 7 x ngenes: then bedf = sum be + 1 with be
+ * = (bmatw edf(theta_b))^power at the cell's level modes; bwvar = sum e (count - mu_b)^2 /
+ * (mu_b + mu_b^2 / theta_b + exp(fail.r)) / sum be (the dataset-wide e, as line 1601 reads);
+ * rowSums(bmatw); bwvar / wvar.
+ * modes_dev ((1 + nbatch) x ngenes: dataset-wide, then per level), matw_dev, bmatw_dev (ngenes
+ * x ncells column-major, a gene contiguous): device memory, or all three NULL for what the last
+ * weights call on ctx left (an error when its shape differs).  models: ncells x 12 col-major,
+ * host.  Sums run in a fixed order: the same input gives the same bits. */
+int scde_pagoda_varnorm_moments_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                                    const double* models, int local_theta, const double* modes_dev,
+                                    const double* matw_dev, const double* bmatw_dev, const int* batch_codes,
+                                    int nbatch, const double* edf_table, int edf_n, double edf_lt0, double edf_h,
+                                    double theta_lo, double theta_hi, double weight_df_power, double* out);
+/* The same on host counts, modes and weights (ctx may be NULL: the default context). */
+int scde_pagoda_varnorm_moments_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                                     const double* models, int local_theta, const double* modes, const double* matw,
+                                     const double* bmatw, const int* batch_codes, int nbatch, const double* edf_table,
+                                     int edf_n, double edf_lt0, double edf_h, double theta_lo, double theta_hi,
+                                     double weight_df_power, double* out);
+
+/* pagoda.varnorm, last stage (R/functions.R:1725-1804): w = 1 - weight_k (1 - matw) divided by
+ * its row sum; x = log10(exp((log(count) - corr.b_i) / corr.a_i) + 1); ov = weightedMatVar(x, w)
+ * (5062-5093, centred, weight-normalised); vr = arv / ov, 0 where ov <= 0; mat = (x - sum x w /
+ * sum w) sqrt(vr).  With a batch (matw_dev is then bmatw) first, per level: the count of x > 0,
+ * wsu(k, n, qnorm(1 - 1e-2)) (1720-1723), their minimum nbub, the level's weights scaled by
+ * pmin(1, ceiling(nbub n_level) / k_level), x minus the level's rowMeans(x w nr) (nr = ncells /
+ * sum w) plus the dataset mean rowMeans(x w) nr (1740-1772); the centring uses the scaled
+ * weights.  arv: host, ngenes (NaN for a gene outside the fit: its mat row is NaN).  mat,
+ * matw_out: host, ngenes x ncells column-major.  matw_dev: device, or NULL for what the last
+ * weights call left (bmatw with a batch).  A batch level without cells is an error. */
+int scde_pagoda_varnorm_matrix_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                                   const double* models, const double* matw_dev, const int* batch_codes, int nbatch,
+                                   double weight_k, const double* arv, double* mat, double* matw_out);
+int scde_pagoda_varnorm_matrix_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                                    const double* models, const double* matw, const int* batch_codes, int nbatch,
+                                    double weight_k, const double* arv, double* mat, double* matw_out);
+
+/* pagoda.subtract.aspect (R/functions.R:1850-1862) on ngenes x ncells column-major matrices (a
+ * gene contiguous): v = the aspect (host, ncells) minus its mean, scaled to unit length; nr =
+ * (mat * matw) v / (matw v^2); out = mat - nr v', then (center) minus rowSums(out * matw) /
+ * rowSums(matw).  _dev: mat, matw and out in device memory (out may not overlap them). */
+int scde_pagoda_subtract_aspect_dev(scde_ctx* ctx, const double* mat_dev, const double* matw_dev, int ngenes,
+                                    int ncells, const double* aspect, int center, double* out_dev);
+int scde_pagoda_subtract_aspect_host(scde_ctx* ctx, const double* mat, const double* matw, int ngenes, int ncells,
+                                     const double* aspect, int center, double* out);
+
 /* scde.expression.prior (R/functions.R:225-254; replaces the R-level function, which has
  * no .Call) on device-resident counts (ngenes x ncells int32, column stride ld).  models:
  * ncells x 12 col-major (conc.b, conc.a, ..., corr.b, corr.a, ..., conc.a2 at column 11 when

@@ -25,6 +25,9 @@ EXPORTS = [
     "scde_expression_difference_batch_dev", "scde_expression_prior_dev",
     "scde_expression_difference_host", "scde_expression_difference_batch_host", "scde_posteriors_host",
     "scde_pagoda_varnorm_weights_dev", "scde_pagoda_varnorm_weights_host",
+    "scde_pagoda_varnorm_moments_dev", "scde_pagoda_varnorm_moments_host",
+    "scde_pagoda_varnorm_matrix_dev", "scde_pagoda_varnorm_matrix_host",
+    "scde_pagoda_subtract_aspect_dev", "scde_pagoda_subtract_aspect_host",
     "scde_baileyWPCA", "scde_bwpca_batch_dev", "scde_r_set_seed", "scde_r_unif_rand", "scde_r_sample",
     "scde_shuffle_perms", "scde_winsorizeMatrix", "scde_matWCorr", "scde_matCorr", "scde_plSemicompleteCor2",
     "scde_wcorr_sep_dev", "scde_wcorr_sep_host", "scde_reciprocal_corr_dev", "scde_reciprocal_corr_host",
@@ -120,6 +123,12 @@ def lib():
                                        P]
     L.scde_pagoda_varnorm_weights_dev.argtypes = [P, P, i64, i, i, P, i, i, P, i, i, i, P, i, i, P, P, P]
     L.scde_pagoda_varnorm_weights_host.argtypes = [P, P, i64, i, i, P, i, i, P, i, i, i, P, i, i, P, P, P]
+    L.scde_pagoda_varnorm_moments_dev.argtypes = L.scde_pagoda_varnorm_moments_host.argtypes = [
+        P, P, i64, i, i, P, i, P, P, P, P, i, P, i, d, d, d, d, d, P]
+    L.scde_pagoda_varnorm_matrix_dev.argtypes = L.scde_pagoda_varnorm_matrix_host.argtypes = [
+        P, P, i64, i, i, P, P, P, i, d, P, P, P]
+    L.scde_pagoda_subtract_aspect_dev.argtypes = L.scde_pagoda_subtract_aspect_host.argtypes = [
+        P, P, P, i, i, P, i, P]
     L.scde_expression_prior_dev.argtypes = [P, P, i64, i, i, P, i, i, d, d, d, P, P, P, P, P, P]
     L.scde_posteriors_dev.argtypes = [P, P, i64, i, P, i, P, i, i, P, i, i, i, i64, i64, i, i, P, P, P, i, P, P, P]
     L.scde_baileyWPCA.argtypes = [P, P, i, i, i, i, i, d, i, P, i, P, P, P, P, P, P, P]

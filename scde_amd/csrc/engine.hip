@@ -270,6 +270,11 @@ struct scde_ctx {
   // aspect redundancy reduction (aspects.hip): staged host matrices (r, n, cr), the patterns
   // scaled to unit length, the collapse kernel's cluster lists, workspace and per-cluster results
   Buf as_r, as_n, as_cr, as_z, as_prob, as_ws, as_out;
+  // pagoda.varnorm: the weights stage's modes and weight matrices kept in HBM for the moments
+  // and matrix stages (vn_n x vn_c, vn_nb levels: what the last weights call left), the edf
+  // table, the cell lists, the per-level scratch, mat / matw before they go to the host
+  Buf vn_modes, vn_matw, vn_bmatw, vn_tab, vn_int, vn_ws, vn_vec, vn_mat, vn_wout;
+  int vn_n = -1, vn_c = -1, vn_nb = 0;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters
@@ -584,6 +589,7 @@ struct scde_ctx {
                  &hc_in,    &hc_ws,      &hc_prob, &hc_out,
                  &gr_raw,   &gr_int,     &gr_prob, &gr_ws,     &gr_out,
                  &as_r,     &as_n,       &as_cr,   &as_z,      &as_prob,   &as_ws,     &as_out,
+                 &vn_modes, &vn_matw,    &vn_bmatw, &vn_tab,   &vn_int,    &vn_ws,     &vn_vec,   &vn_mat,  &vn_wout,
                  &w8t,      &w8g,      &qflags,  &gkey,     &gkey2,    &gidx,     &gorder,  &gwork,   &pmask,  &pwide,  &excd, &gdone};
     for (Buf* b : wp) b->release();
     for (auto& u : us) u.release();
@@ -3568,10 +3574,11 @@ int scde_pagoda_varnorm_weights_dev(scde_ctx* ctx, const int* counts_dev, int64_
                                     int nbatch, int use_expected_value, double* modes, double* matw,
                                     double* bmatw) {
   FORK_GUARD();
-  if (!ctx || !counts_dev || !models || !prior_x || !modes || !matw) return fail(SCDE_EARG, "null argument");
+  if (!ctx || !counts_dev || !models || !prior_x || !modes) return fail(SCDE_EARG, "null argument");
   if (ngenes < 0 || ncells <= 0 || ngrid <= 0 || ld < ngenes) return fail(SCDE_EARG, "bad dimensions");
   const bool batch = batch_codes && nbatch > 1;
-  if (batch && !bmatw) return fail(SCDE_EARG, "bmatw required with a batch");
+  if (batch && matw && !bmatw) return fail(SCDE_EARG, "bmatw required with a batch");
+  ctx->vn_n = -1;  // what the context keeps for the later stages is valid once this call has finished
   HCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int N = ngenes, C = ncells, G = ngrid;
@@ -3585,9 +3592,9 @@ int scde_pagoda_varnorm_weights_dev(scde_ctx* ctx, const int* counts_dev, int64_
   }
   RCHK(upload(ctx, ctx->diffv, mag.data(), sizeof(double) * G));
   const int nm = batch ? 1 + nbatch : 1;
-  HCHK(ctx->res.ensure(sizeof(double) * std::max<size_t>(1, (size_t)N * nm)));
+  HCHK(ctx->vn_modes.ensure(sizeof(double) * std::max<size_t>(1, (size_t)N * nm)));
   HCHK(ctx->jpB.ensure(sizeof(double) * std::max<size_t>(1, (size_t)N * G)));
-  double* dmodes = ctx->res.as<double>();
+  double* dmodes = ctx->vn_modes.as<double>();
   std::vector<int> allc(C);
   for (int c = 0; c < C; ++c) allc[c] = c;
   // dataset-wide modes, then one set per batch level
@@ -3612,21 +3619,27 @@ int scde_pagoda_varnorm_weights_dev(scde_ctx* ctx, const int* counts_dev, int64_
   // weight matrices
   RCHK(upload(ctx, ctx->models, models, sizeof(double) * (size_t)C * 12));
   RCHK(upload(ctx, ctx->in1, allc.data(), sizeof(int) * C));
-  HCHK(ctx->outbuf.ensure(sizeof(double) * std::max<size_t>(1, (size_t)N * C)));
+  // (the matrices stay in the context for scde_pagoda_varnorm_moments_dev / _matrix_dev)
   std::vector<long long> off(C, 0);
   for (int pass = 0; pass < (batch ? 2 : 1); ++pass) {
+    Buf& keep = pass == 0 ? ctx->vn_matw : ctx->vn_bmatw;
+    HCHK(keep.ensure(sizeof(double) * std::max<size_t>(1, (size_t)N * C)));
     if (pass == 1)
       for (int c = 0; c < C; ++c) off[c] = (long long)(1 + batch_codes[c]) * N;
     RCHK(upload(ctx, ctx->in2, off.data(), sizeof(long long) * C));
     HCHK(launch_vn_matw(counts_dev, ld, N, ctx->in1.as<int>(), C, ctx->models.as<double>(), C, square_logit_conc,
-                        dmodes, ctx->in2.as<long long>(), ctx->outbuf.as<double>(), st));
-    if ((size_t)N * C)
-      HCHK(hipMemcpyAsync(pass == 0 ? matw : bmatw, ctx->outbuf.p, sizeof(double) * (size_t)N * C,
-                          hipMemcpyDeviceToHost, st));
-    RCHK(ctx->sync());  // outbuf / in2 are reused by the next pass
+                        dmodes, ctx->in2.as<long long>(), keep.as<double>(), st));
+    double* host = pass == 0 ? matw : bmatw;
+    if (host && (size_t)N * C)
+      HCHK(hipMemcpyAsync(host, keep.p, sizeof(double) * (size_t)N * C, hipMemcpyDeviceToHost, st));
+    RCHK(ctx->sync());  // in2 is reused by the next pass
   }
   if (N) HCHK(hipMemcpyAsync(modes, dmodes, sizeof(double) * (size_t)N * nm, hipMemcpyDeviceToHost, st));
-  return ctx->sync();
+  RCHK(ctx->sync());
+  ctx->vn_n = N;
+  ctx->vn_c = C;
+  ctx->vn_nb = batch ? nbatch : 0;
+  return SCDE_OK;
 }
 
 int scde_pagoda_varnorm_weights_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
@@ -3640,6 +3653,233 @@ int scde_pagoda_varnorm_weights_host(scde_ctx* ctx, const int* counts, int64_t l
   return scde_pagoda_varnorm_weights_dev(ctx, dev, ngenes, ngenes, ncells, models, local_theta, square_logit_conc,
                                          prior_x, ngrid, nboot, n_cores, batch_codes, nbatch, use_expected_value,
                                          modes, matw, bmatw);
+}
+
+// pagoda.varnorm after its weights (varnorm.hip).  The weights come from the caller or, with
+// null pointers, from what the last weights call on this context left in HBM.
+static int vn_retained(scde_ctx* ctx, int N, int C, int nb, const char* who) {
+  if (ctx->vn_n != N || ctx->vn_c != C || ctx->vn_nb != nb)
+    return fail(SCDE_EARG,
+                "%s: no weights given and the context holds none of this shape (scde_pagoda_varnorm_weights_dev "
+                "left %d x %d with %d levels; asked for %d x %d with %d)",
+                who, ctx->vn_n, ctx->vn_c, ctx->vn_nb, N, C, nb);
+  return SCDE_OK;
+}
+
+static int vn_check_codes(const int* codes, int C, int nb) {
+  for (int c = 0; c < C; ++c)
+    if (codes[c] < 0 || codes[c] >= nb) return fail(SCDE_EARG, "batch code out of range");
+  return SCDE_OK;
+}
+
+int scde_pagoda_varnorm_moments_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                                    const double* models, int local_theta, const double* modes_dev,
+                                    const double* matw_dev, const double* bmatw_dev, const int* batch_codes,
+                                    int nbatch, const double* edf_table, int edf_n, double edf_lt0, double edf_h,
+                                    double theta_lo, double theta_hi, double weight_df_power, double* out) {
+  FORK_GUARD();
+  if (!ctx || !counts_dev || !models || !edf_table || !out) return fail(SCDE_EARG, "varnorm_moments: null argument");
+  if (ngenes < 0 || ncells <= 0 || ld < ngenes) return fail(SCDE_EARG, "varnorm_moments: bad dimensions");
+  if (edf_n < 2 || !(edf_h > 0.0) || !std::isfinite(edf_lt0))
+    return fail(SCDE_EARG, "varnorm_moments: the edf table needs at least 2 points on an increasing uniform grid");
+  const bool batch = batch_codes && nbatch > 1;
+  const int nb = batch ? nbatch : 0;
+  if (batch) RCHK(vn_check_codes(batch_codes, ncells, nbatch));
+  if (!modes_dev && !matw_dev && !bmatw_dev) {
+    RCHK(vn_retained(ctx, ngenes, ncells, nb, "varnorm_moments"));
+    modes_dev = ctx->vn_modes.as<double>();
+    matw_dev = ctx->vn_matw.as<double>();
+    bmatw_dev = batch ? ctx->vn_bmatw.as<double>() : nullptr;
+  } else if (!modes_dev || !matw_dev || (batch && !bmatw_dev)) {
+    return fail(SCDE_EARG, "varnorm_moments: modes, matw (and bmatw with a batch) go together");
+  }
+  if (!batch) bmatw_dev = nullptr;
+  const int N = ngenes, C = ncells;
+  if (N == 0) return SCDE_OK;
+  HCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  RCHK(upload(ctx, ctx->models, models, sizeof(double) * (size_t)C * 12));
+  RCHK(upload(ctx, ctx->vn_tab, edf_table, sizeof(double) * 2 * (size_t)edf_n));
+  if (batch) RCHK(upload(ctx, ctx->vn_int, batch_codes, sizeof(int) * C));
+  const int nq = batch ? 7 : 3;
+  HCHK(ctx->vn_vec.ensure(sizeof(double) * (size_t)N * nq));
+  const VnEdf edf{ctx->vn_tab.as<double>(), ctx->vn_tab.as<double>() + edf_n, edf_n, edf_lt0, edf_h};
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_varnorm_moments(counts_dev, ld, N, C, ctx->models.as<double>(), local_theta, modes_dev, matw_dev,
+                              bmatw_dev, batch ? ctx->vn_int.as<int>() : nullptr, edf, theta_lo, theta_hi,
+                              weight_df_power, ctx->vn_vec.as<double>(), st));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(out, ctx->vn_vec.p, sizeof(double) * (size_t)N * nq, hipMemcpyDeviceToHost, st));
+  return ctx->sync();
+}
+
+// host weights into the context's buffers (they become what the context holds)
+static int vn_stage_weights(scde_ctx* ctx, int N, int C, int nb, const double* modes, const double* matw,
+                            const double* bmatw) {
+  ctx->vn_n = -1;
+  const size_t nc = sizeof(double) * (size_t)N * C;
+  HCHK(ctx->vn_matw.ensure(std::max<size_t>(1, nc)));
+  if (nb) HCHK(ctx->vn_bmatw.ensure(std::max<size_t>(1, nc)));
+  if (nc) {
+    HCHK(hipMemcpyAsync(ctx->vn_matw.p, matw, nc, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HCHK(hipMemcpyAsync(ctx->vn_bmatw.p, bmatw, nc, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (modes) {
+    const size_t nmb = sizeof(double) * (size_t)N * (1 + nb);
+    HCHK(ctx->vn_modes.ensure(std::max<size_t>(1, nmb)));
+    if (nmb) HCHK(hipMemcpyAsync(ctx->vn_modes.p, modes, nmb, hipMemcpyHostToDevice, ctx->stream));
+  }
+  RCHK(ctx->sync());
+  if (modes) {
+    ctx->vn_n = N;
+    ctx->vn_c = C;
+    ctx->vn_nb = nb;
+  }
+  return SCDE_OK;
+}
+
+int scde_pagoda_varnorm_moments_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                                     const double* models, int local_theta, const double* modes, const double* matw,
+                                     const double* bmatw, const int* batch_codes, int nbatch, const double* edf_table,
+                                     int edf_n, double edf_lt0, double edf_h, double theta_lo, double theta_hi,
+                                     double weight_df_power, double* out) {
+  FORK_GUARD();
+  const bool batch = batch_codes && nbatch > 1;
+  if (!modes || !matw || (batch && !bmatw)) return fail(SCDE_EARG, "varnorm_moments: null argument");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  RCHK(vn_stage_weights(ctx, ngenes, ncells, batch ? nbatch : 0, modes, matw, bmatw));
+  return scde_pagoda_varnorm_moments_dev(ctx, dev, ngenes, ngenes, ncells, models, local_theta,
+                                         ctx->vn_modes.as<double>(), ctx->vn_matw.as<double>(),
+                                         batch ? ctx->vn_bmatw.as<double>() : nullptr, batch_codes, nbatch, edf_table,
+                                         edf_n, edf_lt0, edf_h, theta_lo, theta_hi, weight_df_power, out);
+}
+
+int scde_pagoda_varnorm_matrix_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                                   const double* models, const double* matw_dev, const int* batch_codes, int nbatch,
+                                   double weight_k, const double* arv, double* mat, double* matw_out) {
+  FORK_GUARD();
+  if (!ctx || !counts_dev || !models || !arv || !mat || !matw_out)
+    return fail(SCDE_EARG, "varnorm_matrix: null argument");
+  if (ngenes < 0 || ncells <= 0 || ld < ngenes) return fail(SCDE_EARG, "varnorm_matrix: bad dimensions");
+  const bool batch = batch_codes && nbatch > 1;
+  const int nb = batch ? nbatch : 0;
+  if (batch) RCHK(vn_check_codes(batch_codes, ncells, nbatch));
+  if (!matw_dev) {
+    RCHK(vn_retained(ctx, ngenes, ncells, nb, "varnorm_matrix"));
+    matw_dev = batch ? ctx->vn_bmatw.as<double>() : ctx->vn_matw.as<double>();
+  }
+  const int N = ngenes, C = ncells;
+  if (N == 0) return SCDE_OK;
+  // the cells grouped by level, in cell order within a level: order[C], then lev_off[nlev + 1]
+  const int nlev = batch ? nbatch : 1;
+  std::vector<int> lists((size_t)C + nlev + 1);
+  int* order = lists.data();
+  int* off = lists.data() + C;
+  int pos = 0;
+  for (int L = 0; L < nlev; ++L) {
+    off[L] = pos;
+    for (int c = 0; c < C; ++c)
+      if (!batch || batch_codes[c] == L) order[pos++] = c;
+    if (pos == off[L]) return fail(SCDE_EARG, "varnorm_matrix: batch level %d has no cells", L);
+  }
+  off[nlev] = pos;
+  HCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t nc = sizeof(double) * (size_t)N * C;
+  if (ctx->vn_mat.ensure(nc) != hipSuccess || ctx->vn_wout.ensure(nc) != hipSuccess ||
+      ctx->vn_ws.ensure(sizeof(double) * 3 * (size_t)nlev * N) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "varnorm_matrix: out of memory: mat and matw need %zu bytes of device memory", 2 * nc);
+  }
+  RCHK(upload(ctx, ctx->models, models, sizeof(double) * (size_t)C * 12));
+  RCHK(upload(ctx, ctx->vn_int, lists.data(), sizeof(int) * lists.size()));
+  RCHK(upload(ctx, ctx->vn_vec, arv, sizeof(double) * N));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_varnorm_matrix(counts_dev, ld, N, C, ctx->models.as<double>(), ctx->vn_int.as<int>(),
+                             ctx->vn_int.as<int>() + C, nlev, batch ? 1 : 0, matw_dev, weight_k,
+                             ctx->vn_vec.as<double>(), ctx->vn_ws.as<double>(), ctx->vn_mat.as<double>(),
+                             ctx->vn_wout.as<double>(), st));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(mat, ctx->vn_mat.p, nc, hipMemcpyDeviceToHost, st));
+  HCHK(hipMemcpyAsync(matw_out, ctx->vn_wout.p, nc, hipMemcpyDeviceToHost, st));
+  const int rc = ctx->sync();
+  if (nc > ((size_t)1 << 30)) {  // two matrices of more than 1 GB each are not kept
+    ctx->vn_mat.release();
+    ctx->vn_wout.release();
+  }
+  return rc;
+}
+
+int scde_pagoda_varnorm_matrix_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                                    const double* models, const double* matw, const int* batch_codes, int nbatch,
+                                    double weight_k, const double* arv, double* mat, double* matw_out) {
+  FORK_GUARD();
+  if (!matw) return fail(SCDE_EARG, "varnorm_matrix: null argument");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  // (without modes the context holds no complete set afterwards: a later call must bring its own)
+  RCHK(vn_stage_weights(ctx, ngenes, ncells, 0, nullptr, matw, nullptr));
+  return scde_pagoda_varnorm_matrix_dev(ctx, dev, ngenes, ngenes, ncells, models, ctx->vn_matw.as<double>(),
+                                        batch_codes, nbatch, weight_k, arv, mat, matw_out);
+}
+
+// pagoda.subtract.aspect (R/functions.R:1850-1862): the aspect centred and scaled to unit
+// length on the host (C values), the rest in k_subtract_aspect.
+static int vn_aspect_unit(const double* aspect, int C, std::vector<double>& v) {
+  v.assign(aspect, aspect + C);
+  double mean = 0.0;
+  for (int c = 0; c < C; ++c) mean += v[c];
+  mean /= C;
+  double ss = 0.0;
+  for (int c = 0; c < C; ++c) {
+    v[c] -= mean;
+    ss += v[c] * v[c];
+  }
+  const double nrm = std::sqrt(ss);
+  for (int c = 0; c < C; ++c) v[c] /= nrm;
+  return SCDE_OK;
+}
+
+int scde_pagoda_subtract_aspect_dev(scde_ctx* ctx, const double* mat_dev, const double* matw_dev, int ngenes,
+                                    int ncells, const double* aspect, int center, double* out_dev) {
+  FORK_GUARD();
+  if (!mat_dev || !matw_dev || !aspect || !out_dev) return fail(SCDE_EARG, "subtract_aspect: null argument");
+  if (ngenes < 0 || ncells <= 0) return fail(SCDE_EARG, "subtract_aspect: bad dimensions");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  if (ngenes == 0) return SCDE_OK;
+  HCHK(hipSetDevice(ctx->device));
+  std::vector<double> v;
+  RCHK(vn_aspect_unit(aspect, ncells, v));
+  RCHK(upload(ctx, ctx->vn_vec, v.data(), sizeof(double) * ncells));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_subtract_aspect(mat_dev, matw_dev, ngenes, ncells, ctx->vn_vec.as<double>(), center, out_dev,
+                              ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return ctx->sync();
+}
+
+int scde_pagoda_subtract_aspect_host(scde_ctx* ctx, const double* mat, const double* matw, int ngenes, int ncells,
+                                     const double* aspect, int center, double* out) {
+  FORK_GUARD();
+  if (!mat || !matw || !aspect || !out) return fail(SCDE_EARG, "subtract_aspect: null argument");
+  if (ngenes < 0 || ncells <= 0) return fail(SCDE_EARG, "subtract_aspect: bad dimensions");
+  if (!ctx) RCHK(default_ctx(&ctx));
+  if (ngenes == 0) return SCDE_OK;
+  HCHK(hipSetDevice(ctx->device));
+  const size_t nc = sizeof(double) * (size_t)ngenes * ncells;
+  if (ctx->vn_mat.ensure(nc) != hipSuccess || ctx->vn_wout.ensure(nc) != hipSuccess ||
+      ctx->pg_a.ensure(nc) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SCDE_EHIP, "subtract_aspect: out of memory: three %d x %d matrices need %zu bytes of device memory",
+                ngenes, ncells, 3 * nc);
+  }
+  HCHK(hipMemcpyAsync(ctx->vn_mat.p, mat, nc, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(hipMemcpyAsync(ctx->vn_wout.p, matw, nc, hipMemcpyHostToDevice, ctx->stream));
+  RCHK(scde_pagoda_subtract_aspect_dev(ctx, ctx->vn_mat.as<double>(), ctx->vn_wout.as<double>(), ngenes, ncells,
+                                       aspect, center, ctx->pg_a.as<double>()));
+  HCHK(hipMemcpyAsync(out, ctx->pg_a.p, nc, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
 }
 
 // ------------------------------------------------------------------ BH (host)

@@ -400,6 +400,31 @@ hipError_t launch_vn_matw(const int* counts, long long ld, int ngenes, const int
                           const double* models, int mld, int sq, const double* modes, const long long* mode_off,
                           double* matw, hipStream_t s);
 
+// ---- pagoda.varnorm after the weights, pagoda.subtract.aspect (varnorm.hip; contract in
+// include/scde_hip.h).  Matrices N x C column-major, a gene contiguous; models C x 12.
+// The edf table on the device: n values y and second derivatives m2 of the natural cubic
+// spline of log(edf) over the uniform grid lt0 + i h of log(theta)
+struct VnEdf {
+  const double* y;
+  const double* m2;
+  int n;
+  double lt0, h;
+};
+// out: 3 x N (edf, wvar, rowSums(matw)), with bmatw / codes 7 x N (+ bedf, bwvar, rowSums(bmatw),
+// bwvar / wvar); modes: (1 + levels) x N
+hipError_t launch_varnorm_moments(const int* counts, long long ld, int N, int C, const double* models, int local_theta,
+                                  const double* modes, const double* matw, const double* bmatw, const int* codes,
+                                  const VnEdf& edf, double th_lo, double th_hi, double power, double* out,
+                                  hipStream_t s);
+// order / lev_off: the cells grouped by level (one level of all cells without a batch); wsrc:
+// matw, or bmatw with a batch; ws: 3 x nlev x N doubles of scratch
+hipError_t launch_varnorm_matrix(const int* counts, long long ld, int N, int C, const double* models, const int* order,
+                                 const int* lev_off, int nlev, int batched, const double* wsrc, double weight_k,
+                                 const double* arv, double* ws, double* mat, double* matw_out, hipStream_t s);
+// v: the aspect, centred and of unit length
+hipError_t launch_subtract_aspect(const double* mat, const double* matw, int N, int C, const double* v, int center,
+                                  double* out, hipStream_t s);
+
 // ---- drop-out-adjusted cell-to-cell correlations (dist.hip; vignettes/diffexp.md:231-301).
 // Matrices genes x cells column-major; cellp: 5 x C (corr.b, corr.a, conc.b, conc.a, conc.a2).
 // x = log10(cd + 1), fpm = scde.expression.magnitude, pself = scde.failure.probability at fpm

@@ -1,10 +1,11 @@
 """Minimal reader for R's serialized `.rda` files (RDX2/RDX3, XDR binary).
 
 Used only to turn the reference's example datasets (`data/es.mef.small.rda`,
-`data/o.ifm.rda`, `data/knn.rda`) into small numpy fixtures under
+`data/o.ifm.rda`, `data/knn.rda`, `data/scde.edff.rda`) into small numpy fixtures under
 `tests/golden/`.  It executes nothing from the file: it is a pure data parser
 for the subset of the R serialization format those files use (pairlists,
-symbols, atomic vectors, lists, attributes, references).
+symbols, atomic vectors, lists, attributes, references, and byte-compiled
+closures, whose code is read past and never run).
 
 Format notes (R Internals, "Serialization Formats"):
   * the file is gzip/bzip2/xz compressed; payload starts with ``RDX2\n`` or
@@ -37,6 +38,9 @@ ATTRLANGSXP = 240
 ATTRLISTSXP = 239
 ALTREP_SXP = 238
 REFSXP = 255
+BCODESXP = 21
+BCREPDEF = 244
+BCREPREF = 243
 
 NA_INTEGER = -(2 ** 31)
 
@@ -86,6 +90,42 @@ class _Reader:
         b = self.buf[self.pos:self.pos + n]
         self.pos += n
         return b
+
+    def _bc_body(self, reps):
+        """A bytecode body: the code vector, then a counted list of typed constants."""
+        code = self.item()
+        consts = []
+        for _ in range(self.int()):
+            t = self.int()
+            if t == BCODESXP:
+                consts.append(self._bc_body(reps))
+            elif t in (6, 2, ATTRLANGSXP, ATTRLISTSXP, BCREPDEF, BCREPREF):
+                consts.append(self._bc_lang(t, reps))
+            else:
+                consts.append(self.item())
+        return RObject(BCODESXP, (code, consts))
+
+    def _bc_lang(self, t, reps):
+        """A language/list node inside a bytecode constant pool (shared nodes go through
+        the reps table: BCREPDEF defines entry `pos`, BCREPREF refers to one)."""
+        if t == BCREPREF:
+            return reps[self.int()]
+        if t not in (6, 2, ATTRLANGSXP, ATTRLISTSXP, BCREPDEF):
+            return self.item()
+        pos = -1
+        if t == BCREPDEF:
+            pos = self.int()
+            t = self.int()
+        node = RObject(6 if t in (6, ATTRLANGSXP) else 2, None)
+        if pos >= 0:
+            reps[pos] = node
+        if t in (ATTRLANGSXP, ATTRLISTSXP):
+            node.attrs = _pairlist_to_dict(self.item())
+        tag = self.item()
+        car = self._bc_lang(self.int(), reps)
+        cdr = self._bc_lang(self.int(), reps)
+        node.value = (tag, car, cdr)
+        return node
 
     def item(self):
         flags = self.int()
@@ -139,6 +179,15 @@ class _Reader:
             if attrs is not None:
                 node.attrs = _pairlist_to_dict(attrs)
             return node
+        if t == BCODESXP:  # byte-compiled closure body: parsed for its length, code kept as data
+            reps = [None] * self.int()
+            o = self._bc_body(reps)
+            if has_attr:
+                o.attrs = _pairlist_to_dict(self.item())
+            return o
+        if t in (7, 8):  # SPECIALSXP, BUILTINSXP: the primitive's name
+            n = self.int()
+            return RObject(t, self.bytes(n).decode("utf-8", "replace"))
         if t == 9:  # CHARSXP
             n = self.int()
             if n == -1:
