@@ -1,0 +1,507 @@
+// api_cluster.hip -- the host side of dist.hip, hclust.hip, olo.hip and tsne.hip: the cell-to-cell
+// distance measures, hierarchical clustering, optimal leaf ordering, exact t-SNE.  (engine.hip is
+// the pipeline; a feature's host code lives in the api_ file named after its kernel files.)
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "engine_internal.h"
+#include "kernels.h"
+
+using namespace scde;
+using namespace scde::host;
+
+extern "C" {
+
+// ------------------------------------------------------------------ cell-to-cell distance measures
+// The vignette's "Adjusted distance measures" (vignettes/diffexp.md:231-301) on the device
+// (dist.hip).  Arguments are checked before the GPU is touched.
+static int dist_check(const void* in, int64_t ld, int ngenes, int ncells, const double* models, const double* out) {
+  if (!in || !models || !out) return fail(SCDE_EARG, "null argument");
+  if (ncells < 1) return fail(SCDE_EARG, "ncells must be at least 1");
+  if (ngenes < 0 || ld < ngenes) return fail(SCDE_EARG, "bad dimensions");
+  return SCDE_OK;
+}
+
+// per-cell constants corr.b, corr.a, conc.b, conc.a, conc.a2 (model columns 3, 4, 0, 1, 11)
+static int dist_cellp(scde_ctx* ctx, const double* models, int C, int sq) {
+  std::vector<double> cellp((size_t)5 * C);
+  const int mcol[5] = {3, 4, 0, 1, 11};
+  for (int j = 0; j < 5; ++j)
+    for (int c = 0; c < C; ++c) cellp[(size_t)j * C + c] = (j == 4 && !sq) ? 0.0 : models[(size_t)mcol[j] * C + c];
+  return upload(ctx, ctx->ds_cell, cellp.data(), sizeof(double) * cellp.size());
+}
+
+static int dist_out(scde_ctx* ctx, int C, double* out) {
+  HCHK(hipMemcpyAsync(out, ctx->ds_out.p, sizeof(double) * (size_t)C * C, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_wcorr_sep_dev(scde_ctx* ctx, const double* x_dev, const double* u_dev, int64_t ld, int ngenes, int ncells,
+                       double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(x_dev, ld, ngenes, ncells, u_dev, out));
+  RCHK(use_ctx(ctx));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)ncells * ncells));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);  // the pair kernels are timed in slot "other"
+  HCHK(launch_wcorr_gram(x_dev, u_dev, ld, ngenes, ncells, ctx->ds_out.as<double>(), 0, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return dist_out(ctx, ncells, out);
+}
+
+int scde_wcorr_sep_host(scde_ctx* ctx, const double* x, const double* u, int64_t ld, int ngenes, int ncells,
+                        double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(x, ld, ngenes, ncells, u, out));
+  RCHK(use_ctx(ctx));
+  RCHK(put_matrix(ctx, ctx->ds_x, x, ld, ngenes, ncells));
+  RCHK(put_matrix(ctx, ctx->ds_u, u, ld, ngenes, ncells));
+  return scde_wcorr_sep_dev(ctx, ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ngenes, ngenes, ncells, out);
+}
+
+int scde_reciprocal_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const double* models, int square_logit_conc, double k, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts_dev, ld, ngenes, ncells, models, out));
+  if (!(k >= 0 && k <= 1)) return fail(SCDE_EARG, "k must be in [0, 1]");
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells, sq = square_logit_conc != 0;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)N * C);
+  RCHK(dist_cellp(ctx, models, C, sq));
+  HCHK(ctx->ds_x.ensure(nb));
+  HCHK(ctx->ds_f.ensure(nb));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)C * C));
+  HCHK(launch_dist_prep(counts_dev, ld, N, C, ctx->ds_cell.as<double>(), sq, ctx->ds_x.as<double>(),
+                        ctx->ds_f.as<double>(), nullptr, ctx->stream));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_recip_corr(ctx->ds_x.as<double>(), ctx->ds_f.as<double>(), N, C, ctx->ds_cell.as<double>(), sq, k,
+                         ctx->ds_out.as<double>(), ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return dist_out(ctx, C, out);
+}
+
+int scde_reciprocal_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const double* models, int square_logit_conc, double k, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts, ld, ngenes, ncells, models, out));
+  if (!(k >= 0 && k <= 1)) return fail(SCDE_EARG, "k must be in [0, 1]");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_reciprocal_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, k, out);
+}
+
+int scde_mode_fail_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                            const double* models, int square_logit_conc, const double* modes,
+                            const double* jp_modes, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts_dev, ld, ngenes, ncells, models, out));
+  if (!modes || !jp_modes) return fail(SCDE_EARG, "null argument");
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells, sq = square_logit_conc != 0;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)N * C);
+  RCHK(dist_cellp(ctx, models, C, sq));
+  RCHK(put_matrix(ctx, ctx->ds_f, modes, N, N, C));
+  RCHK(put_matrix(ctx, ctx->ds_jpm, jp_modes, N, N, 1));
+  HCHK(ctx->ds_x.ensure(nb));
+  HCHK(ctx->ds_u.ensure(nb));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)C * C));
+  HCHK(launch_dist_mode_prep(counts_dev, ld, N, C, ctx->ds_cell.as<double>(), sq, ctx->ds_f.as<double>(),
+                             ctx->ds_jpm.as<double>(), ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ctx->stream));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_wcorr_gram(ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), N, N, C, ctx->ds_out.as<double>(), 0,
+                         ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return dist_out(ctx, C, out);
+}
+
+int scde_mode_fail_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                             const double* models, int square_logit_conc, const double* modes,
+                             const double* jp_modes, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts, ld, ngenes, ncells, models, out));
+  if (!modes || !jp_modes) return fail(SCDE_EARG, "null argument");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_mode_fail_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, modes, jp_modes, out);
+}
+
+static int direct_check(double k, int nsim) {
+  if (!(k >= 0 && k <= 1)) return fail(SCDE_EARG, "k must be in [0, 1]");
+  if (nsim < 1) return fail(SCDE_EARG, "nsim must be at least 1");
+  return SCDE_OK;
+}
+
+int scde_direct_corr_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                         const double* models, int square_logit_conc, double k, int nsim, const double* uniforms,
+                         uint64_t seed, double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts_dev, ld, ngenes, ncells, models, out));
+  RCHK(direct_check(k, nsim));
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells, sq = square_logit_conc != 0;
+  const long long NC = (long long)N * C;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)NC);
+  RCHK(dist_cellp(ctx, models, C, sq));
+  HCHK(ctx->ds_x0.ensure(nb));
+  HCHK(ctx->ds_p.ensure(nb));
+  HCHK(ctx->ds_x.ensure(nb));
+  HCHK(ctx->ds_u.ensure(nb));
+  if (uniforms) HCHK(ctx->ds_f.ensure(nb));
+  HCHK(ctx->ds_out.ensure(sizeof(double) * (size_t)C * C));
+  HCHK(launch_dist_prep(counts_dev, ld, N, C, ctx->ds_cell.as<double>(), sq, ctx->ds_x0.as<double>(), nullptr,
+                        ctx->ds_p.as<double>(), ctx->stream));
+  // the rounds run one after the other on the stream and add into the result in round order
+  for (int s = 0; s < nsim; ++s) {
+    if (uniforms && NC)
+      HCHK(hipMemcpyAsync(ctx->ds_f.p, uniforms + (size_t)s * NC, sizeof(double) * NC, hipMemcpyHostToDevice,
+                          ctx->stream));
+    HCHK(launch_dist_direct_prep(ctx->ds_x0.as<double>(), ctx->ds_p.as<double>(), NC, k,
+                                 uniforms ? ctx->ds_f.as<double>() : nullptr, dist_sim_key(seed, s),
+                                 ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ctx->stream));
+    hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+    HCHK(launch_wcorr_gram(ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), N, N, C, ctx->ds_out.as<double>(), s > 0,
+                           ctx->stream));
+    ctx->mark_end(SLOT_OTHER, ev);
+  }
+  RCHK(dist_out(ctx, C, out));
+  for (size_t e = 0; e < (size_t)C * C; ++e) out[e] /= (double)nsim;
+  return SCDE_OK;
+}
+
+int scde_direct_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* models,
+                          int square_logit_conc, double k, int nsim, const double* uniforms, uint64_t seed,
+                          double* out) {
+  FORK_GUARD();
+  RCHK(dist_check(counts, ld, ngenes, ncells, models, out));
+  RCHK(direct_check(k, nsim));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_direct_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, k, nsim, uniforms, seed,
+                              out);
+}
+
+// ------------------------------------------------------------------ hierarchical clustering
+// stats::hclust / cutree's tree for the monotone linkages (hclust.hip; contract in scde_hip.h).
+// Arguments are checked before the GPU is touched.
+
+// a host n x n matrix (hclust's, order.optimal's) into hc_in; the caller drops it afterwards
+// (drop_square) when it is more than 1 GB
+static int stage_square(scde_ctx* ctx, const double* d, int64_t ld, int n, const char* who) {
+  if (ctx->hc_in.ensure(sizeof(double) * (size_t)n * n) != hipSuccess)
+    return fail_oom("%s: out of memory: the matrix needs %zu bytes of device memory", who,
+                    sizeof(double) * (size_t)n * n);
+  return put_matrix(ctx, ctx->hc_in, d, ld, n, n);
+}
+
+static void drop_square(scde_ctx* ctx, int n) {
+  if (sizeof(double) * (size_t)n * n > ((size_t)1 << 30)) ctx->hc_in.release();
+}
+
+static int hclust_run(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int64_t* ldv,
+                      const int* n, int method, int* merge, double* height, int* order) {
+  RCHK(use_ctx(ctx));
+  std::vector<HclustProblem> pr(nprob);
+  size_t wsb = 0, steps = 0;
+  for (int p = 0; p < nprob; ++p) {
+    pr[p] = {(long long)off[p], (long long)ldv[p], (long long)wsb, (long long)steps, n[p]};
+    wsb += hclust_ws_bytes(n[p]);
+    steps += (size_t)n[p] - 1;
+  }
+  // the workspace comes first: a problem that does not fit fails here, before any launch
+  if (ctx->hc_ws.ensure(wsb) != hipSuccess)
+    return fail_oom("hclust: out of memory: the workspace of %d problem(s) needs %zu bytes of device memory",
+                    nprob, wsb);
+  RCHK(upload(ctx, ctx->hc_prob, pr.data(), sizeof(HclustProblem) * pr.size()));
+  // oh (doubles), flags (long long), oi, oj (ints)
+  const size_t ob = steps * (sizeof(double) + 2 * sizeof(int)) + sizeof(long long) * nprob;
+  HCHK(ctx->hc_out.ensure(ob));
+  double* oh = ctx->hc_out.as<double>();
+  long long* flag = reinterpret_cast<long long*>(oh + steps);
+  int* oi = reinterpret_cast<int*>(flag + nprob);
+  int* oj = oi + steps;
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_hclust(d_dev, ctx->hc_prob.as<HclustProblem>(), nprob, method, ctx->hc_ws.as<char>(), oi, oj, oh, flag,
+                     ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  std::vector<char> host(ob);
+  HCHK(hipMemcpyAsync(host.data(), ctx->hc_out.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  if (wsb > ((size_t)1 << 30)) ctx->hc_ws.release();  // a 20,000-object workspace is 3.2 GB: not kept
+  const double* hh = reinterpret_cast<const double*>(host.data());
+  const long long* hf = reinterpret_cast<const long long*>(hh + steps);
+  const int* hi = reinterpret_cast<const int*>(hf + nprob);
+  const int* hj = hi + steps;
+  for (int p = 0; p < nprob; ++p) {
+    if (hf[p] >= 0)
+      return fail(SCDE_EARG, "hclust: problem %d: non-finite distance at row %lld, column %lld (1-based)", p,
+                  hf[p] % n[p] + 1, hf[p] / n[p] + 1);
+    if (hf[p] != -1)
+      return fail(SCDE_EINTERNAL, "hclust: problem %d: no pair to merge at step %lld", p, -2 - hf[p]);
+  }
+  size_t so = 0, oo = 0;
+  for (int p = 0; p < nprob; ++p) {
+    hclust_encode(n[p], hi + so, hj + so, hh + so, method, merge + 2 * so, height + so, order + oo);
+    so += (size_t)n[p] - 1;
+    oo += (size_t)n[p];
+  }
+  return SCDE_OK;
+}
+
+static int hclust_check(const void* d, int64_t ld, int n, int method, const void* merge, const void* height,
+                        const void* order) {
+  if (!d || !merge || !height || !order) return fail(SCDE_EARG, "null argument");
+  if (n < 2) return fail(SCDE_EARG, "hclust: at least 2 objects are needed (n = %d)", n);
+  if (ld < n) return fail(SCDE_EARG, "hclust: ld must be at least n");
+  if (method < 0 || method > 5)
+    return fail(SCDE_EARG, "hclust: unknown method code %d (0 ward.D, 1 ward.D2, 2 single, 3 complete, 4 average, "
+                "5 mcquitty)", method);
+  return SCDE_OK;
+}
+
+int scde_hclust_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, int method, int* merge, double* height,
+                    int* order) {
+  FORK_GUARD();
+  RCHK(hclust_check(d_dev, ld, n, method, merge, height, order));
+  const int64_t off = 0;
+  return hclust_run(ctx, 1, d_dev, &off, &ld, &n, method, merge, height, order);
+}
+
+int scde_hclust_host(scde_ctx* ctx, const double* d, int64_t ld, int n, int method, int* merge, double* height,
+                     int* order) {
+  FORK_GUARD();
+  RCHK(hclust_check(d, ld, n, method, merge, height, order));
+  RCHK(use_ctx(ctx));
+  RCHK(stage_square(ctx, d, ld, n, "hclust"));
+  const int64_t off = 0, ldn = n;
+  const int rc = hclust_run(ctx, 1, ctx->hc_in.as<double>(), &off, &ldn, &n, method, merge, height, order);
+  drop_square(ctx, n);
+  return rc;
+}
+
+int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int* n,
+                          int method, int* merge, double* height, int* order) {
+  FORK_GUARD();
+  if (nprob < 0) return fail(SCDE_EARG, "hclust: nprob must not be negative");
+  if (nprob == 0) return SCDE_OK;
+  if (!off || !n) return fail(SCDE_EARG, "null argument");
+  std::vector<int64_t> ldv(nprob);
+  for (int p = 0; p < nprob; ++p) {
+    if (off[p] < 0) return fail(SCDE_EARG, "hclust: problem %d: negative offset", p);
+    RCHK(hclust_check(d_dev, n[p], n[p], method, merge, height, order));
+    ldv[p] = n[p];
+  }
+  return hclust_run(ctx, nprob, d_dev, off, ldv.data(), n, method, merge, height, order);
+}
+
+// ------------------------------------------------------------------ optimal leaf ordering
+// cba::order.optimal (olo.hip; contract in scde_hip.h).  The arguments and the merge matrix are
+// checked on the host before the GPU is touched.
+static int olo_check(const void* d, int64_t ld, int n, const int* merge, const int* merge_out, const int* order_out) {
+  if (!d || !merge || !merge_out || !order_out) return fail(SCDE_EARG, "null argument");
+  if (n < 2) return fail(SCDE_EARG, "order.optimal: at least 2 objects are needed (n = %d)", n);
+  if (ld < n) return fail(SCDE_EARG, "order.optimal: ld must be at least n");
+  const uintptr_t mb = (uintptr_t)merge, mob = (uintptr_t)merge_out, oob = (uintptr_t)order_out;
+  const uintptr_t me = mb + sizeof(int) * 2 * (size_t)(n - 1), moe = mob + sizeof(int) * 2 * (size_t)(n - 1),
+                  ooe = oob + sizeof(int) * (size_t)n;
+  if ((mob < me && mb < moe) || (oob < me && mb < ooe) || (oob < moe && mob < ooe))
+    return fail(SCDE_EARG, "order.optimal: merge_out and order_out must not alias merge or each other");
+  char msg[256];
+  if (olo_check_merge(n, merge, msg, sizeof(msg))) return fail(SCDE_EARG, "%s", msg);
+  return SCDE_OK;
+}
+
+static int olo_run(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, const int* merge, int* merge_out,
+                   int* order_out, double* length) {
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = olo_solve(ctx->stream, d_dev, ld, n, merge, merge_out, order_out, length, ctx->st_olo, msg,
+                           sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  RCHK(ctx->sync());
+  if (rc) return fail(rc == 1 ? SCDE_EARG : rc == 2 ? SCDE_EHIP : SCDE_EINTERNAL, "%s", msg);
+  return SCDE_OK;
+}
+
+int scde_order_optimal_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, const int* merge, int* merge_out,
+                           int* order_out, double* length) {
+  FORK_GUARD();
+  RCHK(olo_check(d_dev, ld, n, merge, merge_out, order_out));
+  RCHK(use_ctx(ctx));
+  return olo_run(ctx, d_dev, ld, n, merge, merge_out, order_out, length);
+}
+
+int scde_order_optimal_host(scde_ctx* ctx, const double* d, int64_t ld, int n, const int* merge, int* merge_out,
+                            int* order_out, double* length) {
+  FORK_GUARD();
+  RCHK(olo_check(d, ld, n, merge, merge_out, order_out));
+  for (int j = 0; j < n - 1; ++j)
+    for (int i = j + 1; i < n; ++i)
+      if (!std::isfinite(d[i + (size_t)j * ld]))
+        return fail(SCDE_EARG, "order.optimal: non-finite distance at row %d, column %d (1-based)", i + 1, j + 1);
+  RCHK(use_ctx(ctx));
+  RCHK(stage_square(ctx, d, ld, n, "order.optimal"));
+  const int rc = olo_run(ctx, ctx->hc_in.as<double>(), n, n, merge, merge_out, order_out, length);
+  drop_square(ctx, n);
+  return rc;
+}
+
+// ------------------------------------------------------------------ exact t-SNE
+// The 2-D embedding of a distance matrix (tsne.hip; contract in scde_hip.h).  Arguments are
+// checked before the GPU is touched.
+static int tsne_check_n(int n) {
+  if (n < 4) return fail(SCDE_EARG, "tsne: at least 4 objects are needed (n = %d)", n);
+  return SCDE_OK;
+}
+
+static int tsne_check_perplexity(int n, double perplexity) {
+  RCHK(tsne_check_n(n));
+  if (!(perplexity >= 1.0) || !(3.0 * perplexity <= (double)(n - 1)))
+    return fail(SCDE_EARG, "tsne: perplexity must be at least 1 and 3 * perplexity at most n - 1 (perplexity = %g, "
+                "n = %d)", perplexity, n);
+  return SCDE_OK;
+}
+
+static int tsne_check_params(const TsneParams& p, int iter0, int niter) {
+  if (!std::isfinite(p.eta) || !std::isfinite(p.exaggeration) || !std::isfinite(p.momentum) ||
+      !std::isfinite(p.final_momentum))
+    return fail(SCDE_EARG, "tsne: eta, exaggeration, momentum and final_momentum must be finite");
+  if (iter0 < 0 || niter < 0) return fail(SCDE_EARG, "tsne: iter0 and the number of iterations must not be negative");
+  return SCDE_OK;
+}
+
+static int tsne_check_ws(int n, const void* ws, int64_t ws_bytes) {
+  if (!ws || ws_bytes < (int64_t)tsne_ws_bytes(n))
+    return fail(SCDE_EARG, "tsne: the workspace is missing or too small (%lld bytes given, scde_tsne_ws_bytes(%d) = "
+                "%zu)", ws ? (long long)ws_bytes : 0ll, n, tsne_ws_bytes(n));
+  if ((uintptr_t)ws & 7) return fail(SCDE_EARG, "tsne: the workspace must be 8-byte aligned");
+  return SCDE_OK;
+}
+
+static int tsne_rc(int rc, const char* msg) {
+  return rc ? fail(rc == 1 ? SCDE_EARG : SCDE_EHIP, "%s", msg) : SCDE_OK;
+}
+
+int scde_tsne_ws_bytes(int n, int64_t* bytes) {
+  if (!bytes) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_n(n));
+  *bytes = (int64_t)tsne_ws_bytes(n);
+  return SCDE_OK;
+}
+
+int scde_tsne_affinities_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, double perplexity, int squared,
+                             double* P_dev, double* beta, void* ws_dev, int64_t ws_bytes) {
+  FORK_GUARD();
+  if (!d_dev || !P_dev || !beta) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_perplexity(n, perplexity));
+  if (ld < n) return fail(SCDE_EARG, "tsne: ld must be at least n");
+  RCHK(tsne_check_ws(n, ws_dev, ws_bytes));
+  RCHK(use_ctx(ctx));
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = tsne_affinities(ctx->stream, d_dev, ld, n, perplexity, squared, P_dev, beta,
+                                 static_cast<char*>(ws_dev), msg, sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return tsne_rc(rc, msg);
+}
+
+int scde_tsne_iterate_dev(scde_ctx* ctx, const double* P_dev, int n, double eta, double exaggeration,
+                          int stop_lying_iter, int mom_switch_iter, double momentum, double final_momentum,
+                          int iter0, int niter, double* Y_dev, double* uY_dev, double* gains_dev, void* ws_dev,
+                          int64_t ws_bytes) {
+  FORK_GUARD();
+  if (!P_dev || !Y_dev || !uY_dev || !gains_dev) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_n(n));
+  const TsneParams prm = {eta, exaggeration, momentum, final_momentum, stop_lying_iter, mom_switch_iter};
+  RCHK(tsne_check_params(prm, iter0, niter));
+  RCHK(tsne_check_ws(n, ws_dev, ws_bytes));
+  if (((uintptr_t)Y_dev | (uintptr_t)uY_dev | (uintptr_t)gains_dev) & 15)
+    return fail(SCDE_EARG, "tsne: Y, uY and gains must be 16-byte aligned");
+  RCHK(use_ctx(ctx));
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = tsne_iterate(ctx->stream, P_dev, n, prm, iter0, niter, Y_dev, uY_dev, gains_dev,
+                              static_cast<char*>(ws_dev), msg, sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return tsne_rc(rc, msg);
+}
+
+int scde_tsne_cost_dev(scde_ctx* ctx, const double* P_dev, int n, const double* Y_dev, double* costs, void* ws_dev,
+                       int64_t ws_bytes) {
+  FORK_GUARD();
+  if (!P_dev || !Y_dev || !costs) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_n(n));
+  RCHK(tsne_check_ws(n, ws_dev, ws_bytes));
+  if ((uintptr_t)Y_dev & 15) return fail(SCDE_EARG, "tsne: Y must be 16-byte aligned");
+  RCHK(use_ctx(ctx));
+  char msg[256] = "";
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  const int rc = tsne_cost(ctx->stream, P_dev, n, Y_dev, costs, static_cast<char*>(ws_dev), msg, sizeof(msg));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return tsne_rc(rc, msg);
+}
+
+int scde_tsne_host(scde_ctx* ctx, const double* d, int64_t ld, int n, double perplexity, int squared, double eta,
+                   double exaggeration, int stop_lying_iter, int mom_switch_iter, double momentum,
+                   double final_momentum, int max_iter, uint32_t seed, const double* Y_init, double* Y, double* costs,
+                   double* beta, double* P) {
+  FORK_GUARD();
+  if (!d || !Y || !costs || !beta) return fail(SCDE_EARG, "null argument");
+  RCHK(tsne_check_perplexity(n, perplexity));
+  if (ld < n) return fail(SCDE_EARG, "tsne: ld must be at least n");
+  const TsneParams prm = {eta, exaggeration, momentum, final_momentum, stop_lying_iter, mom_switch_iter};
+  RCHK(tsne_check_params(prm, 0, max_iter));
+  const size_t nn = (size_t)n;
+  std::vector<double> y0(2 * nn);
+  if (Y_init) {
+    std::copy(Y_init, Y_init + 2 * nn, y0.begin());
+  } else {  // 1e-4 * rnorm(2 n) after set.seed(seed), point by point
+    uint32_t state[625];
+    RCHK(scde_r_set_seed(seed, state));
+    RCHK(scde_r_norm_rand(state, (int64_t)(2 * nn), y0.data()));
+    for (double& v : y0) v = 1e-4 * v;
+  }
+  RCHK(use_ctx(ctx));
+  // d, P; then Y, uY, gains; then the workspace: one allocation, freed before the call returns
+  const size_t mat = (sizeof(double) * nn * nn + 255) / 256 * 256, vec = (16 * nn + 255) / 256 * 256;
+  const size_t total = 2 * mat + 3 * vec + tsne_ws_bytes(n);
+  char* base = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&base), total) != hipSuccess)
+    return fail_oom("tsne: out of memory: %d objects need %zu bytes of device memory", n, total);
+  double *dd = reinterpret_cast<double*>(base), *Pd = reinterpret_cast<double*>(base + mat),
+         *Yd = reinterpret_cast<double*>(base + 2 * mat), *Ud = reinterpret_cast<double*>(base + 2 * mat + vec),
+         *Gd = reinterpret_cast<double*>(base + 2 * mat + 2 * vec);
+  char* ws = base + 2 * mat + 3 * vec;
+  char msg[256] = "";
+  hipStream_t st = ctx->stream;
+  std::vector<double> ones(2 * nn, 1.0);
+  int rc = 0;
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+    return e == hipSuccess;
+  };
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  do {
+    const size_t row = sizeof(double) * nn;
+    if (!ok(ld == n ? hipMemcpyAsync(dd, d, row * nn, hipMemcpyHostToDevice, st)
+                    : hipMemcpy2DAsync(dd, row, d, sizeof(double) * (size_t)ld, row, nn, hipMemcpyHostToDevice, st)))
+      break;
+    if (!ok(hipMemcpyAsync(Yd, y0.data(), 16 * nn, hipMemcpyHostToDevice, st))) break;
+    if (!ok(hipMemcpyAsync(Gd, ones.data(), 16 * nn, hipMemcpyHostToDevice, st))) break;
+    if (!ok(hipMemsetAsync(Ud, 0, 16 * nn, st))) break;
+    if ((rc = tsne_affinities(st, dd, n, n, perplexity, squared, Pd, beta, ws, msg, sizeof(msg)))) break;
+    if ((rc = tsne_iterate(st, Pd, n, prm, 0, max_iter, Yd, Ud, Gd, ws, msg, sizeof(msg)))) break;
+    if ((rc = tsne_cost(st, Pd, n, Yd, costs, ws, msg, sizeof(msg)))) break;
+    if (!ok(hipMemcpyAsync(Y, Yd, 16 * nn, hipMemcpyDeviceToHost, st))) break;
+    if (P && !ok(hipMemcpyAsync(P, Pd, sizeof(double) * nn * nn, hipMemcpyDeviceToHost, st))) break;
+    ok(hipStreamSynchronize(st));
+  } while (false);
+  ctx->mark_end(SLOT_OTHER, ev);
+  if (e != hipSuccess || rc) (void)hipStreamSynchronize(st);
+  const hipError_t ef = hipFree(base);
+  if (rc) return tsne_rc(rc, msg);
+  if (e != hipSuccess || ef != hipSuccess)
+    return fail(SCDE_EHIP, "tsne: %s", hipGetErrorString(e != hipSuccess ? e : ef));
+  return SCDE_OK;
+}
+}  // extern "C"

@@ -20,7 +20,7 @@ from test_wpca_oracle import _np_round
 
 from oracle import wpca as W
 
-#: engine.hip, scde_bwpca_batch_dev: kLdsCap -- the EM kernel keeps the working coefficients
+#: api_pagoda.hip, scde_bwpca_batch_dev: kLdsCap -- the EM kernel keeps the working coefficients
 #: in LDS while (dmax + n) * K * sizeof(double) is at most this, else in global scratch
 LDS_CAP = 160 * 1024 - 2048
 

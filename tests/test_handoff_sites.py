@@ -4,16 +4,26 @@ tests/test_gpu_ordering.py makes a missing wait fail deterministically by queuei
 a stream after each of its cross-stream waits (so what it produces next starts late) and before
 each event another stream or host thread waits on (the test hook "handoff_spin",
 include/scde_hip.h).  That only covers the handoffs that call the hook, so this check reads
-engine.hip: each `hipEventRecord` is either one of the profiling marks (timing events of one
-stream, never waited on by another) or is immediately preceded by a `handoff_spin(...)` on the
-same stream, and every `hipStreamWaitEvent` sits inside `handoff_wait`, which spins after the
-wait.  A new handoff added without the hook fails here.
+the library's host code -- engine.hip (the pipeline, which holds every handoff today), the
+feature files api_*.hip and the header they share: each `hipEventRecord` is either one of the
+profiling marks (timing events of one stream, never waited on by another) or is immediately
+preceded by a `handoff_spin(...)` on the same stream, and every `hipStreamWaitEvent` sits inside
+`handoff_wait`, which spins after the wait.  A new handoff added without the hook, in any of
+these files, fails here.
 """
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENGINE = os.path.join(ROOT, "scde_amd", "csrc", "engine.hip")
+CSRC = os.path.join(ROOT, "scde_amd", "csrc")
+ENGINE = os.path.join(CSRC, "engine.hip")
+HOST_FILES = ["engine.hip", "engine_internal.h"] + sorted(f for f in os.listdir(CSRC)
+                                                          if re.fullmatch(r"api_\w+\.hip", f))
+
+
+def _sources():
+    for name in HOST_FILES:
+        yield name, open(os.path.join(CSRC, name)).read()
 
 
 def _records(lines):
@@ -24,17 +34,19 @@ def _records(lines):
 
 
 def test_every_cross_stream_event_is_preceded_by_the_spin_hook():
-    lines = open(ENGINE).read().split("\n")
-    recs = list(_records(lines))
-    assert len(recs) >= 14, recs  # the pipelined host path's handoffs (and the two timing marks)
+    nrecs = 0
     missing = []
-    for i, ev, stream in recs:
-        if ev in ("a", "b") and "(void)" in lines[i]:  # mark_begin / mark_end timing events
-            continue
-        prev = lines[i - 1]
-        m = re.search(r"handoff_spin\(([^,]+),\s*([^)]+)\)", prev)
-        if not m or m.group(2).strip() != stream:
-            missing.append(f"engine.hip:{i + 1}: hipEventRecord({ev}, {stream}) without handoff_spin on {stream}")
+    for name, src in _sources():
+        lines = src.split("\n")
+        for i, ev, stream in _records(lines):
+            nrecs += 1
+            if ev in ("a", "b") and "(void)" in lines[i]:  # mark_begin / mark_end timing events
+                continue
+            prev = lines[i - 1]
+            m = re.search(r"handoff_spin\(([^,]+),\s*([^)]+)\)", prev)
+            if not m or m.group(2).strip() != stream:
+                missing.append(f"{name}:{i + 1}: hipEventRecord({ev}, {stream}) without handoff_spin on {stream}")
+    assert nrecs >= 14, nrecs  # the pipelined host path's handoffs (and the two timing marks)
     assert not missing, "\n".join(missing)
 
 
@@ -45,11 +57,14 @@ def test_every_cross_stream_wait_goes_through_handoff_wait():
     body = m.group(1)
     assert "hipStreamWaitEvent" in body and "handoff_spin" in body
     assert body.index("hipStreamWaitEvent") < body.index("handoff_spin")  # spin after the wait
-    rest = src[: m.start()] + src[m.end():]
-    raw = [f"engine.hip:{src[: src.index(l)].count(chr(10)) + 1}: {l.strip()}"
-           for l in rest.split("\n") if "hipStreamWaitEvent(" in l]
+    raw, nwaits = [], 0
+    for name, text in _sources():
+        rest = text[: m.start()] + text[m.end():] if name == "engine.hip" else text
+        raw += [f"{name}:{text[: text.index(l)].count(chr(10)) + 1}: {l.strip()}"
+                for l in rest.split("\n") if "hipStreamWaitEvent(" in l]
+        nwaits += text.count("handoff_wait(") + text.count("lane_join(")
     assert not raw, "raw waits outside handoff_wait:\n" + "\n".join(raw)
-    assert src.count("handoff_wait(") + src.count("lane_join(") >= 16
+    assert nwaits >= 16
 
 
 def test_spin_hook_is_reachable_from_the_api():
