@@ -829,6 +829,26 @@ int scde_collapse_aspects_dev(scde_ctx* ctx, const double* x_dev, const double* 
                               const int64_t* off, const int* idx, int scale, int pick_top, double* d_dev,
                               double* dw_dev, int* top, int* fallback, double* orientation);
 
+/* ---------------------------------------------------------------- pagoda.top.aspects
+ * The matrix step of pagoda.top.aspects (R/functions.R:2434-2452; csrc/top_aspects.hip, driven by
+ * scde_amd/top_aspects.py; everything before it is host statistics).  x and w are the rows of
+ * t(scores) and t(scoreweights) of the m valid aspects, m x ncells row-major (an aspect's cells
+ * contiguous); num holds one factor per aspect (host, m values): sqrt(qchisq(.) / n.cells), or
+ * the score with use.oe.scale.  Per row r, in float64 as written:
+ *   mean = sum(x[r, ]) / ncells;  var = sum((x[r, ] - mean)^2) / (ncells - 1)   (two passes)
+ *   xv[r, c]  = (x[r, c] - mean) * (num[r] / sqrt(var))
+ *   xvw[r, c] = w[r, c] / sum(w[r, ])
+ * A constant row gives NaN (0 * Inf) in xv, a row of one cell NaN (0 / 0); nothing is clamped.
+ * One launch, one workgroup per row; the sums are added in an order fixed by ncells alone (no
+ * atomics), so results are bit-repeatable and the two entries agree bit for bit.  m >= 0,
+ * ncells >= 1; the four matrices must not overlap.  ctx may be NULL. */
+/* x_dev, w_dev, xv_dev, xvw_dev resident (m x ncells doubles each). */
+int scde_top_aspects_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev, const double* num, int m, int ncells,
+                         double* xv_dev, double* xvw_dev);
+/* The same on host matrices (staged; SCDE_EHIP "out of memory" before any launch). */
+int scde_top_aspects(scde_ctx* ctx, const double* x, const double* w, const double* num, int m, int ncells, double* xv,
+                     double* xvw);
+
 /* Free and total bytes of the context's device (hipMemGetInfo). */
 int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);
 

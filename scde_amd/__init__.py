@@ -18,6 +18,7 @@ from .distance import (direct_dropout_distance, mode_relative_distance, reciproc
                        weighted_correlation)
 from .embedding import TsneState, tsne_affinities, tsne_embedding, tsne_iterate  # noqa: F401
 from .prior import expression_prior  # noqa: F401
+from .top_aspects import pagoda_effective_cells, pagoda_top_aspects, top_aspects_table  # noqa: F401
 from .varnorm import (EdfTable, fit_trend, load_edf_table, pagoda_subtract_aspect, pagoda_varnorm)  # noqa: F401
 
 __version__ = "0.1.0"

@@ -39,6 +39,7 @@ EXPORTS = [
     "scde_matWCorr_distance_dev", "scde_collapse_aspects_dev",
     "scde_order_optimal_host", "scde_order_optimal_dev",
     "scde_tsne_ws_bytes", "scde_tsne_affinities_dev", "scde_tsne_iterate_dev", "scde_tsne_cost_dev", "scde_tsne_host",
+    "scde_top_aspects", "scde_top_aspects_dev",
 ]
 
 
@@ -168,6 +169,7 @@ def lib():
     L.scde_aspect_distance_dev.argtypes = [P, P, i, i, P, i, d, P]
     L.scde_matWCorr_distance_dev.argtypes = [P, P, P, i, i, i, P]
     L.scde_collapse_aspects_dev.argtypes = [P, P, P, i, i, i, P, P, i, i, P, P, P, P, P]
+    L.scde_top_aspects.argtypes = L.scde_top_aspects_dev.argtypes = [P, P, P, P, i, i, P, P]
     _lib = L
     return L
 

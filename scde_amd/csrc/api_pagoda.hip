@@ -1,6 +1,7 @@
-// api_pagoda.hip -- the host side of wpca.hip, pagoda.hip, rnorm.hip, sigma1.hip, aspects.hip and
-// varnorm.hip: weighted PCA, the PAGODA helpers, the random rounds of pagoda.gene.clusters, the
-// aspect redundancy reduction, pagoda.varnorm and pagoda.subtract.aspect.  (engine.hip is the
+// api_pagoda.hip -- the host side of wpca.hip, pagoda.hip, rnorm.hip, sigma1.hip, aspects.hip,
+// varnorm.hip and top_aspects.hip: weighted PCA, the PAGODA helpers, the random rounds of
+// pagoda.gene.clusters, the aspect redundancy reduction, pagoda.varnorm, pagoda.subtract.aspect
+// and the matrix step of pagoda.top.aspects.  (engine.hip is the
 // pipeline; a feature's host code lives in the api_ file named after its kernel files.)
 #include <algorithm>
 #include <cmath>
@@ -1031,6 +1032,49 @@ int scde_pagoda_subtract_aspect_host(scde_ctx* ctx, const double* mat, const dou
   RCHK(scde_pagoda_subtract_aspect_dev(ctx, ctx->vn_mat.as<double>(), ctx->vn_wout.as<double>(), ngenes, ncells,
                                        aspect, center, ctx->pg_a.as<double>()));
   HCHK(hipMemcpyAsync(out, ctx->pg_a.p, nc, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
+}
+
+// ------------------------------------------------------------------ pagoda.top.aspects
+// The matrix step (top_aspects.hip; contract in scde_hip.h).  Arguments are checked before the
+// GPU is touched.
+static int top_aspects_check(const void* x, const void* w, const void* num, int m, int ncells, const void* xv,
+                             const void* xvw) {
+  if (m < 0 || ncells < 1) return fail(SCDE_EARG, "top_aspects: bad dimensions (m = %d, ncells = %d)", m, ncells);
+  if (m > 0 && (!x || !w || !num || !xv || !xvw)) return fail(SCDE_EARG, "top_aspects: null argument");
+  return SCDE_OK;
+}
+
+int scde_top_aspects_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev, const double* num, int m, int ncells,
+                         double* xv_dev, double* xvw_dev) {
+  FORK_GUARD();
+  RCHK(top_aspects_check(x_dev, w_dev, num, m, ncells, xv_dev, xvw_dev));
+  RCHK(use_ctx(ctx));
+  if (m == 0) return SCDE_OK;
+  RCHK(upload(ctx, ctx->ta_num, num, sizeof(double) * (size_t)m));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_top_aspects(x_dev, w_dev, ctx->ta_num.as<double>(), m, ncells, xv_dev, xvw_dev, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return ctx->sync();
+}
+
+int scde_top_aspects(scde_ctx* ctx, const double* x, const double* w, const double* num, int m, int ncells, double* xv,
+                     double* xvw) {
+  FORK_GUARD();
+  RCHK(top_aspects_check(x, w, num, m, ncells, xv, xvw));
+  RCHK(use_ctx(ctx));
+  if (m == 0) return SCDE_OK;
+  const size_t nc = sizeof(double) * (size_t)m * ncells;
+  if (ctx->ta_x.ensure(nc) != hipSuccess || ctx->ta_w.ensure(nc) != hipSuccess || ctx->ta_xv.ensure(nc) != hipSuccess ||
+      ctx->ta_xvw.ensure(nc) != hipSuccess)
+    return fail_oom("top_aspects: out of memory: four %d x %d matrices need %zu bytes of device memory", m, ncells,
+                    4 * nc);
+  HCHK(hipMemcpyAsync(ctx->ta_x.p, x, nc, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(hipMemcpyAsync(ctx->ta_w.p, w, nc, hipMemcpyHostToDevice, ctx->stream));
+  RCHK(scde_top_aspects_dev(ctx, ctx->ta_x.as<double>(), ctx->ta_w.as<double>(), num, m, ncells,
+                            ctx->ta_xv.as<double>(), ctx->ta_xvw.as<double>()));
+  HCHK(hipMemcpyAsync(xv, ctx->ta_xv.p, nc, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(xvw, ctx->ta_xvw.p, nc, hipMemcpyDeviceToHost, ctx->stream));
   return ctx->sync();
 }
 }  // extern "C"

@@ -248,6 +248,8 @@ struct scde_ctx {
   // table, the cell lists, the per-level scratch, mat / matw before they go to the host
   Buf vn_modes, vn_matw, vn_bmatw, vn_tab, vn_int, vn_ws, vn_vec, vn_mat, vn_wout;
   int vn_n = -1, vn_c = -1, vn_nb = 0;
+  // pagoda.top.aspects: the row factors, and the host entry's staged scores, weights and results
+  Buf ta_num, ta_x, ta_w, ta_xv, ta_xvw;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters

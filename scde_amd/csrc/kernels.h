@@ -542,4 +542,10 @@ hipError_t launch_collapse(const double* x, const double* w, int ncells, int m, 
                            const int* idx, const long long* ws_off, double* ws, int scale, int pick_top, double* d,
                            double* wo, int* top, int* status, double* ocor, hipStream_t s);
 
+// ---- pagoda.top.aspects' matrix step (top_aspects.hip; contract in include/scde_hip.h).  x, w,
+// xv, xvw: m x C row-major (an aspect contiguous); num: m values.  Row r of xv is x's row centred
+// times num[r] / sqrt(its variance, denominator C - 1), row r of xvw is w's row over its sum
+hipError_t launch_top_aspects(const double* x, const double* w, const double* num, int m, int C, double* xv,
+                              double* xvw, hipStream_t s);
+
 }  // namespace scde
