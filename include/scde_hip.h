@@ -849,6 +849,51 @@ int scde_top_aspects_dev(scde_ctx* ctx, const double* x_dev, const double* w_dev
 int scde_top_aspects(scde_ctx* ctx, const double* x, const double* w, const double* num, int m, int ncells, double* xv,
                      double* xvw);
 
+/* ---------------------------------------------------------------- knn.error.models, neighbourhood stage
+ * What knn.error.models computes before its mixture fit (R/functions.R:1180-1226; csrc/knn.hip,
+ * driven by scde_amd/knn.py; the fit itself is not part of the library).  counts is int32,
+ * ngenes x ncells column-major with leading dimension ld; thr is min.count.threshold and an entry
+ * is valid when counts[g, j] >= thr.  Counts are not negative (not checked here: a negative
+ * valid count, possible with thr <= 0, gives sqrt's NaN in the similarity and a negative value
+ * in fpm, as R's arithmetic does).  At most 8192 cells: more is SCDE_EARG.  ctx may be NULL.
+ *
+ * Similarity: scde_wcorr_sep of x = sqrt(counts) where valid, 0 elsewhere, and u = valid (both
+ * formed on the device): the pairwise-complete Pearson correlation of the cells, in the one-pass
+ * form written there.  out is ncells x ncells (host), NaN where a pair is degenerate.  The matrix
+ * also stays resident in the context for scde_knn_neighbours. */
+int scde_knn_similarity_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, int thr,
+                            double* out);
+int scde_knn_similarity_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, int thr,
+                             double* out);
+/* Neighbours.  sim is a host ncells x ncells column-major matrix, or NULL for the similarity the
+ * last scde_knn_similarity_* call on this context left resident (it must have ncells cells).
+ * groups (host, ncells codes, NULL: one group) limits cell i's candidates to the other cells of
+ * its group.  Candidate j comes before candidate l when sim[i, j] > sim[i, l], or they are equal
+ * (-0 equals +0) and j < l, or sim[i, l] is NaN and sim[i, j] is not, or both are NaN and j < l:
+ * R's order(decreasing = TRUE).  Row i of out (host, ncells x kmax row-major, int32, 0-based)
+ * receives the first min(k, group size - 1) candidates, then -1; kmax must be at least the
+ * largest of these counts.  Positions are found by counting, so the result is exact and the
+ * same every run.  The lists also stay resident for scde_knn_magnitudes_*. */
+int scde_knn_neighbours(scde_ctx* ctx, const double* sim, int ncells, const int* groups, int k, int kmax, int* out);
+/* Expected magnitudes.  nb is a host ncells x kmax row-major list with entries in [-1, ncells)
+ * (-1: none), or NULL for the lists the last scde_knn_neighbours call left resident (the same
+ * ncells and kmax); ls holds ncells finite library sizes (host), each at least 0 and, when
+ * thr <= 0, above 0 (a valid count over a library size of 0 is Inf, as in R).  For gene g and cell i,
+ * with S = { counts[g, j] / ls[j] : j in nb[i, ], counts[g, j] >= thr } and n = |S|:
+ *   n = 0         fpm[g, i] = NaN
+ *   trim >= 0.5   the median of S (the mean of the two middle values when n is even)
+ *   otherwise     lo = floor(n * trim) + 1 (the product in double), hi = n + 1 - lo, and
+ *                 fpm[g, i] = the mean of the lo-th to hi-th smallest values of S
+ * nabove[g, i] = the number of j in nb[i, ] with counts[g, j] > thr (strictly).  fpm (double)
+ * and nabove (int32) are host ngenes x ncells column-major.  trim >= 0.  Equal values are ordered
+ * by cell index, every sum is taken in an order fixed by the neighbour list alone and there are
+ * no floating-point atomics: results are bit-repeatable and the two entries agree bit for bit.
+ * A row of nb that lists a cell twice is SCDE_EARG. */
+int scde_knn_magnitudes_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const int* nb,
+                            int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove);
+int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const int* nb,
+                             int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove);
+
 /* Free and total bytes of the context's device (hipMemGetInfo). */
 int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);
 

@@ -40,6 +40,8 @@ EXPORTS = [
     "scde_order_optimal_host", "scde_order_optimal_dev",
     "scde_tsne_ws_bytes", "scde_tsne_affinities_dev", "scde_tsne_iterate_dev", "scde_tsne_cost_dev", "scde_tsne_host",
     "scde_top_aspects", "scde_top_aspects_dev",
+    "scde_knn_similarity_dev", "scde_knn_similarity_host", "scde_knn_neighbours",
+    "scde_knn_magnitudes_dev", "scde_knn_magnitudes_host",
 ]
 
 
@@ -170,6 +172,9 @@ def lib():
     L.scde_matWCorr_distance_dev.argtypes = [P, P, P, i, i, i, P]
     L.scde_collapse_aspects_dev.argtypes = [P, P, P, i, i, i, P, P, i, i, P, P, P, P, P]
     L.scde_top_aspects.argtypes = L.scde_top_aspects_dev.argtypes = [P, P, P, P, i, i, P, P]
+    L.scde_knn_similarity_dev.argtypes = L.scde_knn_similarity_host.argtypes = [P, P, i64, i, i, i, P]
+    L.scde_knn_neighbours.argtypes = [P, P, i, P, i, i, P]
+    L.scde_knn_magnitudes_dev.argtypes = L.scde_knn_magnitudes_host.argtypes = [P, P, i64, i, i, P, i, P, i, d, P, P]
     _lib = L
     return L
 

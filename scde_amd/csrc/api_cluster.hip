@@ -504,4 +504,173 @@ int scde_tsne_host(scde_ctx* ctx, const double* d, int64_t ld, int n, double per
     return fail(SCDE_EHIP, "tsne: %s", hipGetErrorString(e != hipSuccess ? e : ef));
   return SCDE_OK;
 }
+
+// ------------------------------------------------------------------ knn.error.models' neighbourhood stage
+// knn.hip; contract in scde_hip.h.  Arguments are checked before the GPU is touched.
+static int knn_check(const void* counts, int64_t ld, int ngenes, int ncells, const char* who) {
+  if (!counts) return fail(SCDE_EARG, "%s: null argument", who);
+  if (ncells < 1 || ngenes < 0 || ld < ngenes)
+    return fail(SCDE_EARG, "%s: bad dimensions (ngenes = %d, ncells = %d)", who, ngenes, ncells);
+  if (ncells > kKnnMaxCells)
+    return fail(SCDE_EARG, "%s: %d cells, at most %d are supported", who, ncells, kKnnMaxCells);
+  return SCDE_OK;
+}
+
+int scde_knn_similarity_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, int thr,
+                            double* out) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "knn_similarity"));
+  if (!out) return fail(SCDE_EARG, "knn_similarity: null argument");
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells;
+  const size_t nb = sizeof(double) * std::max<size_t>(1, (size_t)N * C), cc = sizeof(double) * (size_t)C * C;
+  ctx->kn_sim_c = -1;
+  if (ctx->ds_x.ensure(nb) != hipSuccess || ctx->ds_u.ensure(nb) != hipSuccess || ctx->kn_sim.ensure(cc) != hipSuccess)
+    return fail_oom("knn_similarity: out of memory: two %d x %d matrices and a %d x %d one need %zu bytes", N, C, C, C,
+                    2 * nb + cc);
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_knn_prep(counts_dev, ld, N, C, thr, ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), ctx->stream));
+  HCHK(launch_wcorr_gram(ctx->ds_x.as<double>(), ctx->ds_u.as<double>(), N, N, C, ctx->kn_sim.as<double>(), 0,
+                         ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(out, ctx->kn_sim.p, cc, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  ctx->kn_sim_c = C;
+  return SCDE_OK;
+}
+
+int scde_knn_similarity_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, int thr,
+                             double* out) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "knn_similarity"));
+  if (!out) return fail(SCDE_EARG, "knn_similarity: null argument");
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_knn_similarity_dev(ctx, dev, ngenes, ngenes, ncells, thr, out);
+}
+
+int scde_knn_neighbours(scde_ctx* ctx, const double* sim, int ncells, const int* groups, int k, int kmax, int* out) {
+  FORK_GUARD();
+  const int C = ncells;
+  if (C < 1 || C > kKnnMaxCells)
+    return fail(SCDE_EARG, "knn_neighbours: %d cells, 1 to %d are supported", C, kKnnMaxCells);
+  if (k < 0 || kmax < 0) return fail(SCDE_EARG, "knn_neighbours: k and kmax must not be negative");
+  if (kmax > 0 && !out) return fail(SCDE_EARG, "knn_neighbours: null argument");
+  // groups as codes 0, 1, ... in order of first appearance; each cell's k = min(k, its group - 1)
+  std::vector<int> meta((size_t)2 * C), first, size;
+  for (int c = 0; c < C; ++c) {
+    const int gc = groups ? groups[c] : 0;
+    size_t p = 0;
+    while (p < first.size() && first[p] != gc) ++p;
+    if (p == first.size()) {
+      if (p >= 4096) return fail(SCDE_EARG, "knn_neighbours: more than 4096 groups");
+      first.push_back(gc);
+      size.push_back(0);
+    }
+    meta[c] = (int)p;
+    ++size[p];
+  }
+  int need = 0;
+  for (int c = 0; c < C; ++c) {
+    meta[(size_t)C + c] = std::min(k, size[meta[c]] - 1);
+    need = std::max(need, meta[(size_t)C + c]);
+  }
+  if (kmax < need)
+    return fail(SCDE_EARG, "knn_neighbours: kmax = %d, the largest group needs %d columns", kmax, need);
+  RCHK(use_ctx(ctx));
+  if (!sim && ctx->kn_sim_c != C)
+    return fail(SCDE_EARG, "knn_neighbours: no resident similarity of %d cells (the last one had %d)", C,
+                ctx->kn_sim_c);
+  ctx->kn_nb_c = -1;
+  if (kmax == 0) {
+    ctx->kn_nb_c = C;
+    ctx->kn_nb_k = 0;
+    return SCDE_OK;
+  }
+  if (sim) {
+    ctx->kn_sim_c = -1;
+    HCHK(ctx->kn_sim.ensure(sizeof(double) * (size_t)C * C));
+    HCHK(hipMemcpyAsync(ctx->kn_sim.p, sim, sizeof(double) * (size_t)C * C, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const size_t ob = sizeof(int) * (size_t)C * kmax;
+  HCHK(ctx->kn_nb.ensure(ob));
+  RCHK(upload(ctx, ctx->kn_int, meta.data(), sizeof(int) * meta.size()));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_knn_neighbours(ctx->kn_sim.as<double>(), C, ctx->kn_int.as<int>(), ctx->kn_int.as<int>() + C, kmax,
+                             ctx->kn_nb.as<int>(), ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(out, ctx->kn_nb.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  if (sim) ctx->kn_sim_c = C;
+  ctx->kn_nb_c = C;
+  ctx->kn_nb_k = kmax;
+  return SCDE_OK;
+}
+
+static int knn_mag_check(int ncells, const int* nb, int kmax, const double* ls, int thr, double trim, const void* fpm,
+                         const void* nabove) {
+  if (!ls || !fpm || !nabove) return fail(SCDE_EARG, "knn_magnitudes: null argument");
+  if (kmax < 0) return fail(SCDE_EARG, "knn_magnitudes: kmax must not be negative");
+  if (!(trim >= 0.0)) return fail(SCDE_EARG, "knn_magnitudes: trim must be at least 0");
+  for (int c = 0; c < ncells; ++c)
+    if (!(ls[c] >= 0.0) || std::isinf(ls[c]) || (ls[c] == 0.0 && thr <= 0))  // (0 / 0 has no place in an order)
+      return fail(SCDE_EARG, "knn_magnitudes: library size %d is not a finite number %s 0", c,
+                  thr <= 0 ? "above" : "of at least");
+  if (nb) {
+    std::vector<int> seen((size_t)ncells, -1);  // the last row that listed each cell
+    for (size_t e = 0; e < (size_t)ncells * kmax; ++e) {
+      const int j = nb[e], i = (int)(e / kmax);
+      if (j < -1 || j >= ncells)
+        return fail(SCDE_EARG, "knn_magnitudes: neighbour %d of cell %d is outside [-1, %d)", j, i, ncells);
+      if (j >= 0 && seen[j] == i) return fail(SCDE_EARG, "knn_magnitudes: cell %d lists neighbour %d twice", i, j);
+      if (j >= 0) seen[j] = i;
+    }
+  }
+  return SCDE_OK;
+}
+
+int scde_knn_magnitudes_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const int* nb,
+                            int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "knn_magnitudes"));
+  RCHK(knn_mag_check(ncells, nb, kmax, ls, thr, trim, fpm, nabove));
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells;
+  if (!nb && (ctx->kn_nb_c != C || ctx->kn_nb_k != kmax))
+    return fail(SCDE_EARG, "knn_magnitudes: no resident neighbours of %d cells x %d (the last were %d x %d)", C, kmax,
+                ctx->kn_nb_c, ctx->kn_nb_k);
+  if (N == 0) return SCDE_OK;
+  const size_t nc = (size_t)N * C;
+  if (ctx->kn_fpm.ensure(sizeof(double) * nc) != hipSuccess || ctx->kn_nab.ensure(sizeof(int) * nc) != hipSuccess)
+    return fail_oom("knn_magnitudes: out of memory: the %d x %d results need %zu bytes of device memory", N, C,
+                    12 * nc);
+  if (nb && kmax > 0) {
+    ctx->kn_nb_c = -1;
+    HCHK(ctx->kn_nb.ensure(sizeof(int) * (size_t)C * kmax));
+    HCHK(hipMemcpyAsync(ctx->kn_nb.p, nb, sizeof(int) * (size_t)C * kmax, hipMemcpyHostToDevice, ctx->stream));
+  }
+  RCHK(upload(ctx, ctx->kn_ls, ls, sizeof(double) * (size_t)C));
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_knn_magnitudes(counts_dev, ld, N, C, ctx->kn_nb.as<int>(), kmax, ctx->kn_ls.as<double>(), thr, trim,
+                             ctx->kn_fpm.as<double>(), ctx->kn_nab.as<int>(), ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(fpm, ctx->kn_fpm.p, sizeof(double) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(nabove, ctx->kn_nab.p, sizeof(int) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  if (nb) {
+    ctx->kn_nb_c = C;
+    ctx->kn_nb_k = kmax;
+  }
+  return SCDE_OK;
+}
+
+int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const int* nb,
+                             int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "knn_magnitudes"));
+  RCHK(knn_mag_check(ncells, nb, kmax, ls, thr, trim, fpm, nabove));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_knn_magnitudes_dev(ctx, dev, ngenes, ngenes, ncells, nb, kmax, ls, thr, trim, fpm, nabove);
+}
 }  // extern "C"

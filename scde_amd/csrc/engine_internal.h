@@ -250,6 +250,11 @@ struct scde_ctx {
   int vn_n = -1, vn_c = -1, vn_nb = 0;
   // pagoda.top.aspects: the row factors, and the host entry's staged scores, weights and results
   Buf ta_num, ta_x, ta_w, ta_xv, ta_xvw;
+  // knn.error.models' neighbourhood stage: the similarity (kn_sim_c cells; -1: none), the
+  // neighbour lists (kn_nb_c x kn_nb_k), groups and per-cell k, library sizes, fpm and nabove
+  // before they go to the host
+  Buf kn_sim, kn_nb, kn_int, kn_ls, kn_fpm, kn_nab;
+  int kn_sim_c = -1, kn_nb_c = -1, kn_nb_k = -1;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters

@@ -542,6 +542,17 @@ hipError_t launch_collapse(const double* x, const double* w, int ncells, int m, 
                            const int* idx, const long long* ws_off, double* ws, int scale, int pick_top, double* d,
                            double* wo, int* top, int* status, double* ocor, hipStream_t s);
 
+// ---- knn.error.models' neighbourhood stage (knn.hip; contract in include/scde_hip.h).  counts
+// N x C column-major (ld); x, u, fpm, nabove dense N x C; sim C x C column-major; nb C x kmax
+// row-major with entries in [-1, C).  More than kKnnMaxCells cells: hipErrorInvalidValue.
+constexpr int kKnnMaxCells = 8192;
+hipError_t launch_knn_prep(const int* counts, long long ld, int N, int C, int thr, double* x, double* u,
+                           hipStream_t s);
+hipError_t launch_knn_neighbours(const double* sim, int C, const int* groups, const int* kcell, int kmax, int* out,
+                                 hipStream_t s);
+hipError_t launch_knn_magnitudes(const int* counts, long long ld, int N, int C, const int* nb, int kmax,
+                                 const double* ls, int thr, double trim, double* fpm, int* nabove, hipStream_t s);
+
 // ---- pagoda.top.aspects' matrix step (top_aspects.hip; contract in include/scde_hip.h).  x, w,
 // xv, xvw: m x C row-major (an aspect contiguous); num: m values.  Row r of xv is x's row centred
 // times num[r] / sqrt(its variance, denominator C - 1), row r of xvw is w's row over its sum
