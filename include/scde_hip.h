@@ -59,6 +59,20 @@ int scde_get_rand_kind(void);
  *  outputs    jp    ngenes x ngrid col-major                   (always)
  *             modes ngenes x ncells col-major       (return_post in {1,3})
  *             post  ncells consecutive ngenes x ngrid col-major blocks (return_post in {2,3})
+ *
+ * Deviation from the reference (this entry and every other that forms posterior tables): a model
+ * row for which the reference fills the cell's tables, and with them every row of the joint
+ * posterior, with NaN is refused with SCDE_EARG before any table is formed (layer 1: before
+ * anything is launched), the message naming the model row and the column:
+ *   - corr.a / corr.b whose mean exp(mag corr.a + corr.b) is NaN or infinite at a grid point
+ *     (a non-positive corr.a on a grid whose first magnitude is -inf; corr.b = 800);
+ *   - conc.a / conc.b (conc.a2) whose exponent is NaN at a grid point (conc.a = 0 on such a grid);
+ *   - fail.r NaN;
+ *   - constant theta (corr.theta) NaN, infinite, zero or negative, or so small against the
+ *     largest mean that theta / (theta + mu) rounds to 0 (5e-324);
+ *   - a NaN magnitude.
+ * Finite tables of extreme models (non-positive slopes on a finite grid, cfp = 0 or 1, fail.r
+ * = -inf or overflowing, theta from 1e-8 to 1.7e308) are formed as the reference forms them.
  */
 int scde_logBootPosterior(const double* models, int ncells, const int* ucl_vals, const int64_t* ucl_off,
                           const int* counti, int ngenes, const double* magnitudes, int ngrid, int nboot, int seed,
@@ -205,6 +219,13 @@ int scde_ctx_get_stat(scde_ctx* ctx, const char* name, double* value);
  * use. */
 int scde_ctx_inject_fault(scde_ctx* ctx, const char* where, int count);
 int scde_ctx_reset_stats(scde_ctx* ctx);
+
+/* scde_logBootPosterior on a context of the caller's (its options, its workspace); NULL: the
+ * library's own default context, as scde_logBootPosterior. */
+int scde_logBootPosterior_ctx(scde_ctx* ctx, const double* models, int ncells, const int* ucl_vals,
+                              const int64_t* ucl_off, const int* counti, int ngenes, const double* magnitudes,
+                              int ngrid, int nboot, int seed, int return_post, int local_theta,
+                              int square_logit_conc, int ensemble, double* jp, double* modes, double* post);
 
 /* device buffers owned by the context's allocator */
 int scde_dev_alloc(scde_ctx* ctx, int64_t bytes, void** dptr);

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("SCDE_LIB") or os.path.join(_HERE, "libscde_hip.so")
 # Symbols declared in include/scde_hip.h (checked by tests/test_abi.py).
 EXPORTS = [
     "scde_last_error", "scde_version", "scde_set_rand_kind", "scde_get_rand_kind",
-    "scde_logBootPosterior", "scde_logBootBatchPosterior", "scde_jpmatLogBoot", "scde_jpmatLogBatchBoot",
+    "scde_logBootPosterior", "scde_logBootPosterior_ctx", "scde_logBootBatchPosterior", "scde_jpmatLogBoot", "scde_jpmatLogBatchBoot",
     "scde_matSlideMult", "scde_ratio_summary", "scde_distribution_summary", "scde_bh_cz",
     "scde_ctx_create", "scde_ctx_destroy", "scde_ctx_synchronize", "scde_ctx_set_profiling",
     "scde_ctx_kernel_times", "scde_ctx_reset_kernel_times", "scde_ctx_set_option", "scde_ctx_get_stat",
@@ -92,6 +92,7 @@ def lib():
     L.scde_set_rand_kind.argtypes = [i]
     L.scde_get_rand_kind.restype = i
     L.scde_logBootPosterior.argtypes = [P, i, P, P, P, i, P, i, i, i, i, i, i, i, P, P, P]
+    L.scde_logBootPosterior_ctx.argtypes = [P, P, i, P, P, P, i, P, i, i, i, i, i, i, i, P, P, P]
     L.scde_logBootBatchPosterior.argtypes = [P, i, P, P, P, i, P, i, P, P, P, i, i, i, i, i, i, P, P, P]
     L.scde_jpmatLogBoot.argtypes = [P, i, i, i, i, i, P]
     L.scde_jpmatLogBatchBoot.argtypes = [P, P, P, i, i, i, i, i, P]

@@ -54,8 +54,9 @@ def _flatten_list(lst):
 
 # ================================================================== .Call mirrors
 def logBootPosterior(Models, Ucl, CountsI, Magnitudes, Nboot, Seed, ReturnIndividualPosteriors=0,
-                     LocalThetaFit=0, SquareLogitConc=0, EnsembleProbability=0):
-    """src/jpmatLogBoot.cpp:100.  Returns jp (ngenes x ngrid) or a dict with jp/modes/post."""
+                     LocalThetaFit=0, SquareLogitConc=0, EnsembleProbability=0, ctx=None):
+    """src/jpmatLogBoot.cpp:100.  Returns jp (ngenes x ngrid) or a dict with jp/modes/post.
+    ctx: a Context to run on (its options and workspace); None: the library's own default context."""
     mm = _f64(Models)
     C = mm.shape[0]
     uci = _i32(CountsI)
@@ -67,9 +68,10 @@ def logBootPosterior(Models, Ucl, CountsI, Magnitudes, Nboot, Seed, ReturnIndivi
     jp = np.zeros((N, G), order="F")
     modes = np.zeros((N, C), order="F") if rp in (1, 3) else None
     post = np.zeros(C * N * G) if rp in (2, 3) else None
-    check(lib().scde_logBootPosterior(_p(mm), C, _p(vals), _p(off), _p(uci), N, _p(mag), G, int(Nboot), int(Seed),
-                                      rp, int(LocalThetaFit), int(SquareLogitConc), int(EnsembleProbability),
-                                      _p(jp), _p(modes), _p(post)))
+    check(lib().scde_logBootPosterior_ctx(ctx.handle if ctx is not None else None, _p(mm), C, _p(vals), _p(off),
+                                          _p(uci), N, _p(mag), G, int(Nboot), int(Seed), rp, int(LocalThetaFit),
+                                          int(SquareLogitConc), int(EnsembleProbability), _p(jp), _p(modes),
+                                          _p(post)))
     return _pack(jp, modes, post, rp, C, N, G)
 
 

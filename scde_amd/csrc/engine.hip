@@ -510,6 +510,57 @@ void make_draws(const PostSpec& s, int Bp, std::vector<int>& draws, std::vector<
 
 }  // namespace
 
+// Models whose tables the reference fills with NaN (and with them every joint posterior row of the
+// call) are refused before anything is launched: the tables kernels drop a NaN term (their exps are
+// guarded by fmax / range tests) and would return finite tables instead.  Per cell, as
+// src/jpmatLogBoot.cpp:128-190 forms them: mu = exp(mag corr.a + corr.b) NaN or infinite at a grid
+// point; the concomitant's exponent NaN at a grid point; fail.r NaN; constant theta not a positive
+// finite number, or so small that theta / (theta + mu) rounds to 0.  The exponents are linear (or,
+// with the squared-logit term, a product of linear factors) in the magnitude, so a NaN shows at the
+// smallest or the largest magnitude; mu and theta / (theta + mu) are monotone in it.  O(cells) on
+// the host.  (include/scde_hip.h, deviations.)
+static int check_models(const scde::host::PostSpec& s) {
+  const int C = s.ncells, G = s.G;
+  double mlo = INFINITY, mhi = -INFINITY;
+  for (int k = 0; k < G; ++k) {
+    const double m = s.mag[k];
+    if (m != m) return fail(SCDE_EARG, "magnitudes[%d] is NaN", k);
+    mlo = std::min(mlo, m);
+    mhi = std::max(mhi, m);
+  }
+  auto M = [&](int c, int col) { return s.models[(size_t)c + (size_t)C * col]; };
+  for (int c = 0; c < C; ++c) {
+    const double concb = M(c, 0), conca = M(c, 1), failr = M(c, 2), corrb = M(c, 3), corra = M(c, 4);
+    const double t0 = mlo * corra + corrb, t1 = mhi * corra + corrb;
+    if (t0 != t0 || t1 != t1)
+      return fail(SCDE_EARG, "model row %d: corr.a = %g, corr.b = %g give a NaN mean at magnitude %g", c, corra, corrb,
+                  t0 != t0 ? mlo : mhi);
+    const double z0 = (s.squarelogit ? (conca + mlo * M(c, 11)) * mlo : mlo * conca) + concb;
+    const double z1 = (s.squarelogit ? (conca + mhi * M(c, 11)) * mhi : mhi * conca) + concb;
+    if (z0 != z0 || z1 != z1)
+      return fail(SCDE_EARG, "model row %d: conc.a = %g, conc.b = %g%s give a NaN drop-out term at magnitude %g", c,
+                  conca, concb, s.squarelogit ? " (with conc.a2)" : "", z0 != z0 ? mlo : mhi);
+    if (failr != failr) return fail(SCDE_EARG, "model row %d: fail.r is NaN", c);
+    const double tmax = std::max(t0, t1);
+    const double th = s.localtheta ? 1.0 : M(c, 5);
+    // (fitted models: mu below e^300 and theta above 1e-20 -- nothing can overflow or round to 0,
+    // and the call pays no exp here)
+    if (tmax < 300.0 && th > 1e-20 && th < INFINITY) continue;
+    const double mumax = std::exp(tmax);
+    if (!(mumax < INFINITY))
+      return fail(SCDE_EARG, "model row %d: corr.a = %g, corr.b = %g give an infinite mean on this grid", c, corra,
+                  corrb);
+    if (!s.localtheta) {
+      if (!(th > 0.0) || !(th < INFINITY))
+        return fail(SCDE_EARG, "model row %d: corr.theta = %g is not a positive finite number", c, th);
+      if (!(th / (th + mumax) > 0.0))
+        return fail(SCDE_EARG, "model row %d: corr.theta = %g against a mean of %g gives probability 0", c, th,
+                    mumax);
+    }
+  }
+  return SCDE_OK;
+}
+
 int scde::host::run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std::function<int()>* rest) {
   const int C = s.ncells, G = s.G, N = s.ngenes;
   // cells per call of the kernel choices, the widest cell list (ELL rows), the bootstrap's genes
@@ -522,6 +573,8 @@ int scde::host::run_posterior(scde_ctx* cx, const PostSpec& s, UniqueSet& u, std
   if (s.nboot < 0) return fail(SCDE_EARG, "nboot must be >= 0");
   if (G > 4096) return fail(SCDE_EARG, "ngrid > 4096 unsupported");
   if (s.seeds.empty()) return fail(SCDE_EINTERNAL, "no seed sets");
+  if (!s.models || !s.mag) return fail(SCDE_EARG, "null models or magnitudes");
+  RCHK(check_models(s));
   if (s.batch_call) {
     for (int k = 0; k < s.nbatch; ++k) {
       if (s.comp[k] < 0) return fail(SCDE_EARG, "negative composition");
@@ -1611,7 +1664,7 @@ static int copy_modes_out(scde_ctx* cx, double* host, const double* dev, size_t 
   return SCDE_OK;
 }
 
-static int logboot_common(bool batch, const double* models, int ncells, const int* ucl_vals, const int64_t* ucl_off,
+static int logboot_common(scde_ctx* cx, bool batch, const double* models, int ncells, const int* ucl_vals, const int64_t* ucl_off,
                           const int* counti, int ngenes, const double* magnitudes, int ngrid, const int* batch_vals,
                           const int64_t* batch_off, const int* composition, int nbatch, int nboot, int seed,
                           int return_post, int local_theta, int square_logit_conc, int ensemble, double* jp,
@@ -1627,7 +1680,6 @@ static int logboot_common(bool batch, const double* models, int ncells, const in
         if (batch_vals[i] < 0 || batch_vals[i] >= ncells) return fail(SCDE_EARG, "BatchIL index out of range");
     }
   }
-  scde_ctx* cx = nullptr;
   RCHK(use_ctx(cx));
   const size_t NG = (size_t)ngenes * ngrid;
   PostSpec s;
@@ -1681,7 +1733,17 @@ int scde_logBootPosterior(const double* models, int ncells, const int* ucl_vals,
                           int return_post, int local_theta, int square_logit_conc, int ensemble, double* jp,
                           double* modes, double* post) {
   FORK_GUARD();
-  return logboot_common(false, models, ncells, ucl_vals, ucl_off, counti, ngenes, magnitudes, ngrid, nullptr,
+  return logboot_common(nullptr, false, models, ncells, ucl_vals, ucl_off, counti, ngenes, magnitudes, ngrid, nullptr,
+                        nullptr, nullptr, 0, nboot, seed, return_post, local_theta, square_logit_conc, ensemble, jp,
+                        modes, post);
+}
+
+int scde_logBootPosterior_ctx(scde_ctx* ctx, const double* models, int ncells, const int* ucl_vals,
+                              const int64_t* ucl_off, const int* counti, int ngenes, const double* magnitudes,
+                              int ngrid, int nboot, int seed, int return_post, int local_theta,
+                              int square_logit_conc, int ensemble, double* jp, double* modes, double* post) {
+  FORK_GUARD();
+  return logboot_common(ctx, false, models, ncells, ucl_vals, ucl_off, counti, ngenes, magnitudes, ngrid, nullptr,
                         nullptr, nullptr, 0, nboot, seed, return_post, local_theta, square_logit_conc, ensemble, jp,
                         modes, post);
 }
@@ -1693,7 +1755,7 @@ int scde_logBootBatchPosterior(const double* models, int ncells, const int* ucl_
                                double* jp, double* modes, double* post) {
   FORK_GUARD();
   if (!batch_vals || !batch_off || !composition) return fail(SCDE_EARG, "null batch input");
-  return logboot_common(true, models, ncells, ucl_vals, ucl_off, counti, ngenes, magnitudes, ngrid, batch_vals,
+  return logboot_common(nullptr, true, models, ncells, ucl_vals, ucl_off, counti, ngenes, magnitudes, ngrid, batch_vals,
                         batch_off, composition, nbatch, nboot, seed, return_post, local_theta, square_logit_conc, 0,
                         jp, modes, post);
 }

@@ -8,7 +8,10 @@
 #define SCDE_BOOT_ASMLD 1  // k_boot2 column look-ahead issued from asm with explicit vmcnt waits
 #endif
 #ifndef SCDE_NB_CLOSED
-#define SCDE_NB_CLOSED 1  // the tables' NB log-pmf in closed form (0: nmath's saddle-point form)
+// The tables' NB log-pmf in closed form.  Fixed at 1: k_tables_lpc's lane pass evaluates only the closed
+// form and its fallback staging no longer writes the p, q rows that the saddle-point form of
+// tables_column_reg reads, so a build with 0 would form wrong tables (static_assert next to k_tables_lpc).
+#define SCDE_NB_CLOSED 1
 #endif
 #ifndef SCDE_TAB_WPE
 #define SCDE_TAB_WPE 4  // k_tables_cell occupancy target (waves per SIMD)
@@ -58,6 +61,9 @@ struct TablesArgs {
   double minlogprob;         // -DBL_MAX / ncells / 1.1
   // k_tables_lpc writes its rows (T, D) as non-temporal stores (the same bits)
   int nt_rows;
+  // Rows (T, D): [0, G) values, pads up to the last 64-point stretch zero; k_tables_lpc leaves the
+  // slots [ceil64(G), GS) unwritten (alignment only: no reader goes past the last 32-point tile or
+  // 64-point stretch -- tests/test_gpu_table_edges.py test_stale_slots_between_calls)
   double* T;                 // [ncols][GS] log-posterior columns
   int* maxi;                 // [ncols] argmax (nullable)
   unsigned char* has_clamp;  // [ncols]

@@ -813,7 +813,14 @@ __device__ __forceinline__ void tables_column_reg(const TablesArgs& a, long long
       const bool mixed = !tiny && !(hi - lo > 37.5);
       double r = hi - lsum;
       if (__builtin_amdgcn_ballot_w64(in && (tiny || mixed))) {
-        const double e = fma(sl[kRowCfp * kRS + 64 * j], E, exp_tab(fmax(t1, -746.0), etab));
+        double e = fma(sl[kRowCfp * kRS + 64 * j], E, exp_tab(fmax(t1, -746.0), etab));
+        if (__builtin_amdgcn_ballot_w64(in && tiny)) {
+          // subnormal range: the Poisson term as the reference forms it, exp(log cfp_k + fp - maxp),
+          // rounded once -- cfp_k E would carry the few bits a subnormal E has left
+          const double et = exp_tab(fmax((sl[kRowLcfp * kRS + 64 * j] + fp) - maxp, -746.0), etab) +
+                            exp_tab(fmax(t1, -746.0), etab);
+          e = tiny ? et : e;
+        }
         const double rm = (SCDE_KT_DIAG & 4) ? e - lsum : log_tab(tiny ? e / s : e, lt) - (tiny ? 0.0 : lsum);
         r = (tiny || mixed) ? rm : r;
       }
@@ -943,6 +950,9 @@ constexpr int kLpcLds0 = kLpcR + kLpcRsz;
 constexpr int kLpcLds = kLpcLds0 > kTabRegRows * kRS ? kLpcLds0 : kTabRegRows * kRS;  // (the fallback's rows overlay it)
 static_assert(kLpcRsz >= kTabStagedG + kLpcWaves * 64, "mu and the partials fit region R");
 static_assert(kLpcWaves * 64 * 3 <= kLpcBase, "the combine's arrays overlay the staged rows");
+static_assert(kTabTaskCols <= 64, "k_tables_lpc maps one lane to each column of a task: wider tasks would lose columns");
+static_assert(SCDE_NB_CLOSED, "k_tables_lpc evaluates the closed form only and does not stage the saddle-point form's "
+                              "p, q rows for its tables_column_reg fallback");
 
 template <int BM>
 __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
@@ -1157,7 +1167,12 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
         r = hi - lsum;
         if (!(SCDE_LPC_DIAG & 4) && __builtin_amdgcn_ballot_w64(ok && tm)) {
           double e = fma(lcf.y, E, LPC_EXP(fmax(t1, -746.0)));
-          if (__builtin_amdgcn_ballot_w64(ok && tiny)) e = tiny ? e / sq : e;
+          if (__builtin_amdgcn_ballot_w64(ok && tiny)) {
+            // subnormal range: the Poisson term as the reference forms it, exp(log cfp_k + fp - maxp),
+            // rounded once -- cfp_k E would carry the few bits a subnormal E has left
+            const double et = LPC_EXP(fmax((lcf.x + fp) - maxp, -746.0)) + LPC_EXP(fmax(t1, -746.0));
+            e = tiny ? et / sq : e;
+          }
           const double rm = log_tab(e, lt) - (tiny ? 0.0 : lsum);
           r = tm ? rm : r;
         }
@@ -1269,7 +1284,9 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
     for (int t = (G + kBTile - 1) / kBTile; t < kQTiles; ++t)
       if (ok) a.UQ[(long long)col * kQTiles + t] = packu(0);
   // the columns outside the lane pass: tables_column_reg, over the general staged rows
-  if (mine && !ok) sfb[atomicAdd(&nfb, 1)] = col;
+  // (wave 0 alone lists them: every wave holds the same 64 columns, and a cell that is not lean
+  // leaves all 64 -- four waves listing them would write 256 entries into sfb's 64)
+  if (w == 0 && mine && !ok) sfb[atomicAdd(&nfb, 1)] = col;
   __syncthreads();
   const int nf = nfb;
   if (nf == 0) return;
