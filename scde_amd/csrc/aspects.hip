@@ -38,6 +38,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace scde {
 namespace {
@@ -219,6 +220,7 @@ __global__ __launch_bounds__(256) void k_unit_cols(const double* __restrict__ x,
     s += xc[i];
   }
   diff = __any(diff);
+  // (the butterflies written out: through wave_sum the compiler orders this kernel differently)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const double mean = s / (double)k;
@@ -310,12 +312,6 @@ __global__ __launch_bounds__(256) void k_wdist(double* __restrict__ d, int m, in
 constexpr int kCB = 256;                           // threads per cluster
 constexpr int kCT = 32, kCK = 32, kCS = kCK + 2;   // Gram tile, chunk of the summed side, LDS row stride
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __device__ __forceinline__ double block_sum(double v, double* red) {
   v = wave_sum(v);
   __syncthreads();
@@ -325,25 +321,11 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }
 
 __device__ __forceinline__ double block_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  v = wave_max(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-__device__ __forceinline__ int sturm_count(const double* __restrict__ d, const double* __restrict__ e2, int n,
-                                           double x, double pivmin) {
-  double q = d[0] - x;
-  if (fabs(q) < pivmin) q = -pivmin;
-  int c = q <= 0.0;
-  for (int i = 1; i < n; ++i) {
-    q = d[i] - e2[i - 1] / q - x;
-    if (fabs(q) < pivmin) q = -pivmin;
-    c += q <= 0.0;
-  }
-  return c;
 }
 
 // R's var of the C values at x (stride 1): two passes, every thread of the block gets it

@@ -2,7 +2,8 @@
 //
 // Restates the R glue of the path on the host side (R/functions.R:566-669
 // scde.posteriors, 3491-3531 ratio posterior / Z, 5039-5051 summary / BH) and
-// drives the gfx950 kernels in kernels.hip on one HIP stream per context.
+// drives the gfx950 kernels of kernels.hip, unique.hip, boot.hip and ratio.hip (launchers in
+// kernels.h) on one HIP stream per context.
 //
 // Layout of the library's host code: engine.hip is the pipeline -- the context's lifecycle,
 // options and statistics, the posterior and differential-expression entry points with their

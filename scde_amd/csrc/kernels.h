@@ -1,4 +1,6 @@
-// kernels.h -- argument blocks and launchers for kernels.hip (internal).
+// kernels.h -- argument blocks and launchers of the kernel files (internal): the DE path's stages
+// kernels.hip (the remainder of the one-file source: tables and default bootstrap, still to be
+// split), unique.hip, boot.hip and ratio.hip, then the feature files.
 #pragma once
 
 #ifndef SCDE_BOOT_WPE
@@ -6,12 +8,6 @@
 #endif
 #ifndef SCDE_BOOT_ASMLD
 #define SCDE_BOOT_ASMLD 1  // k_boot2 column look-ahead issued from asm with explicit vmcnt waits
-#endif
-#ifndef SCDE_NB_CLOSED
-// The tables' NB log-pmf in closed form.  Fixed at 1: k_tables_lpc's lane pass evaluates only the closed
-// form and its fallback staging no longer writes the p, q rows that the saddle-point form of
-// tables_column_reg reads, so a build with 0 would form wrong tables (static_assert next to k_tables_lpc).
-#define SCDE_NB_CLOSED 1
 #endif
 #ifndef SCDE_TAB_WPE
 #define SCDE_TAB_WPE 4  // k_tables_cell occupancy target (waves per SIMD)
@@ -46,6 +42,9 @@ constexpr int kColc = 11;
 #define SCDE_TAB_TASK_COLS 64
 #endif
 constexpr int kTabTaskCols = SCDE_TAB_TASK_COLS;
+constexpr int kStretchSlots = 8;  // per-column stretch bounds: ceil(G / 64) <= 7 used
+
+inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 struct TablesArgs {
   const int* ucl;            // flat unique counts, [ncols]
@@ -525,6 +524,20 @@ size_t sigma1_ws_doubles(long long ncols, int ncells);
 hipError_t launch_sigma1sq(const double* x, int ncells, long long ngenes, int nprob, const long long* off,
                            const int* idx, const long long* ws_off, double* ws, double* out, int* flag,
                            hipStream_t s);
+// Sturm count of the pivots <= 0 of T - x I (d: diagonal, e2: squared off-diagonal; dstebz's pivot
+// recurrence): the eigenvalue bisections of sigma1.hip and aspects.hip
+__device__ __forceinline__ int sturm_count(const double* __restrict__ d, const double* __restrict__ e2, int n,
+                                           double x, double pivmin) {
+  double q = d[0] - x;
+  if (fabs(q) < pivmin) q = -pivmin;
+  int c = q <= 0.0;
+  for (int i = 1; i < n; ++i) {
+    q = d[i] - e2[i - 1] / q - x;
+    if (fabs(q) < pivmin) q = -pivmin;
+    c += q <= 0.0;
+  }
+  return c;
+}
 
 // ---- aspect redundancy reduction (aspects.hip; contract in include/scde_hip.h).  Square
 // matrices are m x m column-major; patterns are ncells x m column-major (an aspect contiguous).

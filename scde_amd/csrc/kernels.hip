@@ -1,95 +1,52 @@
-// kernels.hip -- gfx950 (CDNA4) FP64 kernels for the scde differential-
-// expression hot path.  See DESIGN.md for the data layout and rooflines.
+// kernels.hip -- the two hot kernel families of the scde differential-expression path on gfx950
+// (CDNA4, FP64): the posterior tables and the default bootstrap; their launchers are at the end
+// of the file.  This file is what remains of the one-file kernel source, on purpose for now:
+// unique.hip (unique-count set, ELL rows, gathers), boot.hip (reference-layout bootstrap, exact
+// fallback, nboot = 0) and ratio.hip (ratio posterior and summary) were cut out of it; the two
+// families below are still to become tables.hip and boot_fast.hip, each a pure move that
+// tools/isa_diff.py checks, after which this file is gone.  The cross-lane primitives are
+// wave_ops.h's.  See DESIGN.md for the data layout and rooflines.
 //
-//   k_cell_prep      per-cell grid vectors mu, log cfp, log(1-cfp), theta
-//                    (src/jpmatLogBoot.cpp:131-162)
-//   k_tables         per-(cell, unique count) NB/Poisson mixture log-posterior
-//                    column + argmax + clamp (src/jpmatLogBoot.cpp:164-210);
-//                    one wavefront per column, lanes over grid points
-//   k_boot           bootstrap joint posterior (src/jpmatLogBoot.cpp:251-271):
-//                    one workgroup per gene, lanes over grid points, 16
-//                    bootstrap accumulators per lane, draws folded into
-//                    per-cell multiplicities, zero-count baseline
-//   k_boot_exact     reference-order fallback for rows whose sums are
-//                    dominated by clamp values
-//   k_ratio_summary  prior-weighted matSlideMult (src/matSlideMult.cpp:5-23)
-//                    + row normalisation + lb/mle/ub/ce/Z epilogue
-//                    (R/functions.R:3491-3531, 5039-5050)
-//   unique-count builder (R/functions.R:609-610 done on device), ELL entry
-//   builder, modes/post gathers, ensemble and nboot==0 variants.
+// Tables:
+//   k_cell_prep       per-cell grid vectors mu, log cfp, log(1 - cfp), theta, and with a constant
+//                     theta p, q, log p, log q (src/jpmatLogBoot.cpp:131-162)            [default]
+//   k_col_consts      per-column constants of the constant-theta forms, one lane per column [default]
+//   k_tables_lpc      one LANE per column, a block = 64 columns of one cell: column + argmax +
+//                     clamp + fused baseline delta + tile / stretch bounds
+//                     (src/jpmatLogBoot.cpp:164-210); tables_column_reg is its in-kernel fallback
+//                     for the columns outside its form                 [default, phases 0 and 2]
+//   k_tables          one wavefront per column, grid vectors from global memory: phase 1 (each
+//                     cell's count-0 column), the columns k_tables_lpc leaves (slow_only) and
+//                     grids wider than kTabStagedG                           [default, phase 1]
+//   k_tables_cell     the cell-staged column-per-wave form: local theta fits (no per-column
+//                     constants) at G <= kTabStagedG
+//   k_base_cols, k_delta   baseline columns and D = T - T[baseline] as passes of their own (the
+//                     default path has both fused into the tables)
+//   k_baseline_z, k_stretch_zu   the baseline cells' part of the bootstrap rows / stretch bounds
+//   k_ensemble_cols   ensemble: exp(T) / colsum(exp(T))
+// Bootstrap over baseline-delta columns (D) and ELL rows:
+//   k_mult, k_zero    draw multiplicities per (set, cell, boot)                            [default]
+//   k_zuq             the baseline cells' part of the integer tile bounds                  [default]
+//   k_boot_gene       the tile bootstrap's first pass: a 4-wave block per (gene, group of slabs),
+//                     16 rows of 32 grid points shared by the group's slabs                [default]
+//   k_boot_tiles      the list pass behind it: one wave per slab k_boot_gene could not finish,
+//                     four bound tiles each                                                [default]
+//   k_boot2_list, k_boot2   every grid point of a slab: the fallback of the two above (list form
+//                     from 400 cells per call), and with k_stretch_mask the stretch-skipping
+//                     bootstrap of calls without tile bounds            [default as the fallback]
+//   k_stretch_mask    stretch upper bounds on the FP64 matrix cores, for k_boot2
+//   k_sum_partials    the slabs' partial jp rows added in slab order                       [default]
 #include <hip/hip_runtime.h>
-#include <climits>
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <utility>
 
 #include "device_math.h"
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace scde {
-
-// ------------------------------------------------------------------ helpers
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-// arma-style max: NaN never wins (first-max semantics live in the argmax path)
-__device__ __forceinline__ double gt_max(double a, double b) { return (b > a) ? b : a; }
-
-// Whole-wave reductions on VALU only (no LDS round trips): within each 16-lane row by DPP
-// (lane^1, ^2 quad_perm; ^7 row_half_mirror; ^15 row_mirror), then across rows with gfx950's
-// v_permlane16_swap / v_permlane32_swap (each leaves the two halves' values side by side,
-// so one op combines them on every lane).  Every lane ends with the same bits.
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double x) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ void rows_swap16(double& a, double& b) {
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false,
-                                                   false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false,
-                                                   false);
-  a = __hiloint2double((int)hi[0], (int)lo[0]);
-  b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ void rows_swap32(double& a, double& b) {
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false,
-                                                   false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false,
-                                                   false);
-  a = __hiloint2double((int)hi[0], (int)lo[0]);
-  b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-// Maximum over each 16-lane row, on every lane of the row (same DPP partners as above).
-__device__ __forceinline__ int row16_max_i32(int v) {
-  v = max(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true));
-  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true));
-  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true));
-  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, true));
-  return v;
-}
-template <bool MAX>
-__device__ __forceinline__ double wave_allreduce(double v) {
-  auto op = [](double a, double b) { return MAX ? gt_max(a, b) : a + b; };
-  v = op(v, dpp64<0xB1>(v));   // quad_perm [1,0,3,2]: lane ^ 1
-  v = op(v, dpp64<0x4E>(v));   // quad_perm [2,3,0,1]: lane ^ 2
-  v = op(v, dpp64<0x141>(v));  // row_half_mirror
-  v = op(v, dpp64<0x140>(v));  // row_mirror
-  double w = v;
-  rows_swap16(v, w);
-  v = op(v, w);
-  w = v;
-  rows_swap32(v, w);
-  return op(v, w);
-}
 
 // ------------------------------------------------------------------ K0: cell prep
 // models: ncells x 12 column-major (R `mm`), columns per src/jpmatLogBoot.cpp:88-99
@@ -187,7 +144,7 @@ __global__ __launch_bounds__(256) void k_col_consts(const int* __restrict__ ucl,
   const double size = theta[(long long)lo * GS], po = size / (size + x);
   o[8] = log(po);
   o[9] = log(1 - po);
-  // the closed form's column constant (k_tables_lpc, tables_column_reg; SCDE_NB_CLOSED): dnbinom(x; size, p) =
+  // the closed form's column constant (k_tables_lpc, tables_column_reg): dnbinom(x; size, p) =
   // log(size / (size + x)) + dbinom_raw(size, n, p, q) and, as bd0(y, n r) = y log(y / n) - y log r
   // + n r - y with p + q = 1, dbinom_raw = S - lf / 2 - size log(size / n) - nx log(nx / n)
   // + size log p + nx log q: everything but the last two terms is this constant
@@ -198,8 +155,6 @@ __global__ __launch_bounds__(256) void k_col_consts(const int* __restrict__ ucl,
 #define SCDE_KT_DIAG 0  // timing-only builds: 1 trivial dnbinom, 2 no exp, 4 no log, 8 no stores, 16 loop 1
                         // only, 32 staging and constants only, 64 no tile bounds
 #endif
-constexpr int kStretchSlots = 8;  // per-column stretch bounds: ceil(G / 64) <= 7 used
-__device__ __forceinline__ float gt_maxf(float a, float b) { return (b > a) ? b : a; }
 
 // One (cell, unique count) column, one wavefront, lanes over grid points.  The per-cell
 // grid vectors (mu, pq, lcfpr, lcfp, theta) and the baseline column come in as pointers:
@@ -600,38 +555,17 @@ __global__ __launch_bounds__(64 * kTabWaves) __attribute__((amdgpu_waves_per_eu(
 // tables_column_reg: the general register-row column (one wave per column; k_tables_lpc's fallback
 // for the columns outside its form): a column's 401 grid values stay in seven VGPR pairs through
 // the three passes (dnbinom + max, exp + sum, log + stores + tile maxima), the chunk loops
-// unrolled so the LDS reads of different chunks overlap.  Lanes the fast dnbinom does not cover:
-// q == 0 (grid point 0, mu = 0) in line; the rest (p or q out of range, np or nq not a positive
-// finite number) through the exact dnbinom in a pass after the loop, only in waves that have such
-// a lane.  Columns whose constants rule out the fast form (colc n < 0) are left to the gated
-// k_tables pass.
+// unrolled so the LDS reads of different chunks overlap.  The NB log-pmf is the closed form (the
+// only form: it has no lanes that need the exact dnbinom).  Columns whose constants rule out the
+// form (colc n < 0) are left to the gated k_tables pass.
 constexpr int kTabChunks = kTabStagedG / 64;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp32f(float x) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-  v = gt_maxf(v, dpp32f<0xB1>(v));
-  v = gt_maxf(v, dpp32f<0x4E>(v));
-  v = gt_maxf(v, dpp32f<0x141>(v));
-  v = gt_maxf(v, dpp32f<0x140>(v));
-  auto s16 = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
-  v = gt_maxf(__int_as_float((int)s16[0]), __int_as_float((int)s16[1]));
-  auto s32 = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
-  return gt_maxf(__int_as_float((int)s32[0]), __int_as_float((int)s32[1]));
-}
 
 // The staged rows have the fixed stride kTabStagedG (entries G.. are zero pads), so every
 // LDS read is lane * 8 plus an immediate offset: no per-chunk address registers (the
 // compiler would hoist ~8 per chunk out of the column loop and spill them).
 constexpr int kRS = kTabStagedG;
-#if SCDE_NB_CLOSED  // the closed form reads log p, log q only: seven staged rows (four blocks of 4 waves per CU)
+// the closed form reads log p, log q only: seven staged rows (four blocks of 4 waves per CU)
 enum { kRowMu = 0, kRowLP = 1, kRowLQ = 2, kRowLcfpr = 3, kRowCfp = 4, kRowLcfp = 5, kRowBase = 6, kTabRegRows = 7 };
-#else
-enum { kRowMu = 0, kRowP = 1, kRowLP = 3, kRowLQ = 4, kRowLcfpr = 5, kRowCfp = 6, kRowLcfp = 7, kRowBase = 8,
-       kTabRegRows = 9 };
-#endif
 
 // Per grid point k of a column, in log space relative to maxp: t1 = nb_k + log(1 - cfp_k)
 // - maxp (the NB term) and t2 = log cfp_k + fp - maxp (the Poisson term); the reference's
@@ -675,19 +609,9 @@ __device__ __forceinline__ void tables_column_reg(const TablesArgs& a, long long
                                                   const LogTab& lt, int lane, double theta, const double* cc,
                                                   double x, double maxcfp, int bc_u) {
   const int G = GC ? GC : a.G;
-  NbFast nf;
-  nf.n = cc[0];
-  if (!(nf.n > 0.0)) return;  // the gated k_tables pass takes this column
-  nf.nx = cc[1];
-  nf.S = cc[2];
-  nf.hlf = cc[3];
-  nf.lp = cc[4];
-  nf.lXn = cc[5];
-  nf.lnxn = cc[6];
+  if (!(cc[0] > 0.0)) return;  // the gated k_tables pass takes this column
   const double fp = cc[7];
   const double lpo = cc[8], lqo = cc[9];
-  nf.X = theta;
-  nf.ok = true;
   const double po = theta / (theta + x);  // the count's own grid point
   if (SCDE_KT_DIAG & 32) {  // timing diagnostic: staging and constants only
     if (po == 12345.0) a.has_clamp[col] = 1;
@@ -695,7 +619,6 @@ __device__ __forceinline__ void tables_column_reg(const TablesArgs& a, long long
   }
   const double* sl = sm + lane;
   double v[kTabChunks];
-  unsigned badm = 0;
   double lmax = -INFINITY;
 #pragma unroll
   for (int j = 0; j < kTabChunks; ++j) {
@@ -704,72 +627,23 @@ __device__ __forceinline__ void tables_column_reg(const TablesArgs& a, long long
       const int k = lane + 64 * j;
       const bool in = k < G;
       const bool last = (k == G - 1);
-#if SCDE_NB_CLOSED
-      double pr = 0.0, qr = 0.0;  // (the saddle-point form's p, q: not staged)
-#else
-      double pr = sl[kRowP * kRS + 64 * j], qr = sl[(kRowP + 1) * kRS + 64 * j];
-#endif
       double lpr = sl[kRowLP * kRS + 64 * j], lqr = sl[kRowLQ * kRS + 64 * j];
       const double muv = sl[kRowMu * kRS + 64 * j], mnext = sl[kRowMu * kRS + 64 * j + 1];
       const bool over = in && ((!last && x > muv && x < mnext) || (last && x > muv));
       if (__builtin_amdgcn_ballot_w64(over)) {
-        pr = over ? po : pr;
-        qr = over ? 1 - po : qr;
         lpr = over ? lpo : lpr;
         lqr = over ? lqo : lqr;
       }
-      // with n > 0 finite: np > 0 implies p > 0, nq > 0 implies q > 0, p <= 1 keeps np and
-      // nq finite -- the fast form's full validity condition
-      const double np = nf.n * pr, nq = nf.n * qr;
-      const bool bad = in && !(np > 0.0 && nq > 0.0 && pr <= 1.0);
-      double nb;
-      if (SCDE_NB_CLOSED) {
-        // log dnbinom(x; size, p_k) = C + size log p_k + x log q_k (C: the column constant;
-        // count 0: size log p_k, as the x == n branch of dbinom_raw).  p_k, q_k are the same
-        // rounded values the saddle-point form takes, log p_k and log q_k the staged logs;
-        // q_k = 0 (grid point 0) gives -inf for x > 0 and 0 for x = 0, as dbinom_raw.  Against
-        // the saddle-point form the difference is below 2e-11 absolute at counts of 5,000 and
-        // means of 10^5 (log space), far under the 1e-6 parity bar.
-        nb = (x == 0.0) ? nf.X * lpr : fma(x, lqr, fma(nf.X, lpr, cc[10]));
-      } else {
-        nb = (SCDE_KT_DIAG & 1) ? lpr * x + lqr : dnbinom_fast(nf, pr, qr, lpr, lqr);
-        badm |= bad ? (1u << j) : 0u;
-      }
+      // log dnbinom(x; size, p_k) = C + size log p_k + x log q_k (C: the column constant;
+      // count 0: size log p_k, as the x == n branch of dbinom_raw).  p_k, q_k are the same
+      // rounded values the saddle-point form takes, log p_k and log q_k the staged logs;
+      // q_k = 0 (grid point 0) gives -inf for x > 0 and 0 for x = 0, as dbinom_raw.  Against
+      // the saddle-point form the difference is below 2e-11 absolute at counts of 5,000 and
+      // means of 10^5 (log space), far under the 1e-6 parity bar.
+      double nb = (x == 0.0) ? theta * lpr : fma(x, lqr, fma(theta, lpr, cc[10]));
       nb += sl[kRowLcfpr * kRS + 64 * j];
       v[j] = in ? nb : -INFINITY;
-      lmax = gt_max(lmax, (!SCDE_NB_CLOSED && bad) ? -INFINITY : v[j]);
-    }
-  }
-  if (__builtin_amdgcn_ballot_w64(badm != 0)) {
-    // q == 0 (prob 1: grid point 0, mu = 0) in line; other lanes through the exact dnbinom,
-    // one call site (rolled over chunks; the value goes back into its register by selects)
-    const double nbq0 = (nf.X == nf.n) ? nf.lp : -INFINITY;  // R dbinom_raw's q == 0 branch
-#pragma unroll 1
-    for (int j = 0; j < kTabChunks; ++j) {
-      const bool b = (badm >> j) & 1u;
-      if (!__builtin_amdgcn_ballot_w64(b)) continue;
-      double nv = 0.0;
-      if (b) {
-        const int k = lane + 64 * j;
-        const double muv = sm[kRowMu * kRS + k], mnext = sm[kRowMu * kRS + k + 1];
-        const bool last = (k == G - 1);
-        const bool over = (!last && x > muv && x < mnext) || (last && x > muv);
-#if SCDE_NB_CLOSED
-        const double pr = po, qr = 1 - po;  // (never reached: the closed form has no exact-path lanes)
-        (void)over;
-#else
-        const double pr = over ? po : sm[kRowP * kRS + k];
-        const double qr = over ? 1 - po : sm[(kRowP + 1) * kRS + k];
-#endif
-        if (qr == 0.0 && pr == 1.0)
-          nv = nbq0;
-        else
-          nv = dnbinom_log_cold(x, theta, pr);
-        nv += sm[kRowLcfpr * kRS + k];
-        lmax = gt_max(lmax, nv);
-      }
-#pragma unroll
-      for (int i = 0; i < kTabChunks; ++i) v[i] = (b && i == j) ? nv : v[i];
+      lmax = gt_max(lmax, v[j]);
     }
   }
   if (SCDE_KT_DIAG & 16) {  // timing diagnostic: loop 1 only
@@ -888,7 +762,6 @@ __device__ __forceinline__ void tables_column_reg(const TablesArgs& a, long long
   if (lane == 0) a.has_clamp[col] = anyc ? 1 : 0;
 }
 
-
 // ------------------------------------------------------------------ lane-per-column tables (round 6)
 // k_tables_lpc<BM>: the constant-theta FP64 tables (phases 0 and 2, G <= kTabStagedG) with one LANE
 // per (cell, unique count) column.  A block takes 64 columns of one cell; its 4 waves split the grid
@@ -912,29 +785,15 @@ __device__ __forceinline__ void tables_column_reg(const TablesArgs& a, long long
 #ifndef SCDE_LPC_DIAG
 #define SCDE_LPC_DIAG 0  // study builds of k_tables_lpc: 1 no row stores, 2 no pass-2 exps, 4 no mixed points, 8 NaN in [GP, GS)
 #endif
-#ifndef SCDE_LPC_EXP_TAB
-#define SCDE_LPC_EXP_TAB 1  // k_tables_lpc's exps through the 64-entry LDS table (0: exp_poly; measured 0.311 vs 0.300 ms per launch)
-#endif
-#if SCDE_LPC_EXP_TAB
-#define LPC_EXP(d) exp_tab((d), etab)
-#else
-#define LPC_EXP(d) exp_poly(d)
-#endif
-#ifndef SCDE_LPC_TW
-#define SCDE_LPC_TW 1  // k_tables_lpc's rows through a per-wave LDS transpose (0: each lane stores its own column;
-                       // 5 blocks per CU instead of 3, measured 0.342 vs 0.306 ms per launch at config 3)
-#endif
-#ifndef SCDE_LPC_PADLDS
-#define SCDE_LPC_PADLDS 0
-#endif
+// Settled by measurement: the exps go through the 64-entry LDS table (a
+// table-free polynomial exp: 0.311 vs 0.300 ms per launch); the rows go out through a per-wave LDS
+// transpose (each lane storing its own column: 5 blocks per CU instead of 3, but 0.342 vs 0.306 ms
+// per launch at config 3); the log tables are read from global memory, not staged in LDS.
 #ifndef LPC_U12
 #define LPC_U12 4  // k_tables_lpc: unroll of passes 1 and 2
 #endif
 #ifndef LPC_U3
 #define LPC_U3 8  // k_tables_lpc: unroll of pass 3's flush group
-#endif
-#ifndef SCDE_LPC_LTAB_GLOBAL
-#define SCDE_LPC_LTAB_GLOBAL 1  // k_tables_lpc: the log tables read from global memory, not staged in LDS
 #endif
 constexpr int kLpcWaves = 4;
 constexpr int kLpcFlush = 8;              // points per register group (and per transposed flush)
@@ -943,24 +802,19 @@ constexpr int kLpcQB = 0;                 // (log q_k, theta log p_k + log(1 - c
 constexpr int kLpcLC = 2 * kTabStagedG;   // (log cfp_k, cfp_k) pairs
 constexpr int kLpcBase = 4 * kTabStagedG; // the baseline column (phase 2; 0 past the grid)
 constexpr int kLpcR = 5 * kTabStagedG;    // region R: mu_k (the override search), then the passes'
-constexpr int kLpcMu = kLpcR;             // partial maxima / sums, then (SCDE_LPC_TW) the transposes
+constexpr int kLpcMu = kLpcR;             // partial maxima / sums, then the transposes
 constexpr int kLpcPart = kLpcR + kTabStagedG;
-constexpr int kLpcRsz = SCDE_LPC_TW ? kLpcWaves * 64 * kLpcTS : kTabStagedG + kLpcWaves * 64;
+constexpr int kLpcRsz = kLpcWaves * 64 * kLpcTS;
 constexpr int kLpcLds0 = kLpcR + kLpcRsz;
 constexpr int kLpcLds = kLpcLds0 > kTabRegRows * kRS ? kLpcLds0 : kTabRegRows * kRS;  // (the fallback's rows overlay it)
 static_assert(kLpcRsz >= kTabStagedG + kLpcWaves * 64, "mu and the partials fit region R");
 static_assert(kLpcWaves * 64 * 3 <= kLpcBase, "the combine's arrays overlay the staged rows");
 static_assert(kTabTaskCols <= 64, "k_tables_lpc maps one lane to each column of a task: wider tasks would lose columns");
-static_assert(SCDE_NB_CLOSED, "k_tables_lpc evaluates the closed form only and does not stage the saddle-point form's "
-                              "p, q rows for its tables_column_reg fallback");
 
 template <int BM>
 __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
   __shared__ __attribute__((aligned(16))) double lds[kLpcLds];
   __shared__ double etab[64];
-#if !SCDE_LPC_LTAB_GLOBAL
-  __shared__ double ltab[3][97];
-#endif
   __shared__ unsigned suqb[kQTiles];
   // per-wave head / tail parts of bound segments split between two waves: tiles as ceil(256 max),
   // stretches as (float) max -- the form the bound takes anyway
@@ -968,18 +822,10 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
   double(*spart)[64] = reinterpret_cast<double(*)[64]>(lds + kLpcPart);  // per-wave partial maxima, then sums
   __shared__ int sfb[64];
   __shared__ int nfb;
-#if SCDE_LPC_PADLDS
-  __shared__ double padlds[SCDE_LPC_PADLDS];  // occupancy study builds only
-  if (threadIdx.x == 0 && a.G < 0) padlds[a.G & 1] = 0.0;
-#endif
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int GS = a.GS, G = a.G;
-#if SCDE_LPC_LTAB_GLOBAL
   if (threadIdx.x < 64) etab[threadIdx.x] = kExp2Frac64[threadIdx.x];
-#else
-  tables_tabs(etab, ltab);
-#endif
   if (a.gate && *a.gate == 0) return;
   const int4 task = a.tasks[blockIdx.x];
   const int c = task.x;
@@ -1024,13 +870,9 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
     lds[kLpcMu + k] = mu;
   }
   lean = __syncthreads_and(lean);
-#if SCDE_LPC_LTAB_GLOBAL
   // the log tables from global memory (cache-resident; the mixed branch that reads them runs on
   // ~1.5% of the points): 2.3 KB less LDS per block, four blocks per CU instead of three
   const LogTab lt{kLogInvC, kLogCHi, kLogCLo};
-#else
-  const LogTab lt{ltab[0], ltab[1], ltab[2]};
-#endif
   const int zc = (phase == 2) ? tab_zcol(a, c) : -1;
   const double maxcfp = a.cellscal[2 * c];
   const double minlp = a.minlogprob;
@@ -1101,19 +943,19 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
     const double cf = LC[k].y;
     const double t1 = (fma(x, qb.x, qb.y) + c10) - maxp;
     double e = cf * E;
-    if (!(SCDE_LPC_DIAG & 2)) e += LPC_EXP(fmax(t1, -746.0));
+    if (!(SCDE_LPC_DIAG & 2)) e += exp_tab(fmax(t1, -746.0), etab);
     ls += e;
   }
   if (ks >= k0 && ks < k1) {
     const double cf = LC[ks].y, tp = (fma(x, QB[ks].x, QB[ks].y) + c10) - maxp, to = (nb0o + c10) - maxp;
-    ls += (cf * E + LPC_EXP(fmax(to, -746.0))) - (cf * E + LPC_EXP(fmax(tp, -746.0)));
+    ls += (cf * E + exp_tab(fmax(to, -746.0), etab)) - (cf * E + exp_tab(fmax(tp, -746.0), etab));
   }
   __syncthreads();  // (every wave has read spart)
   spart[w][lane] = ls;
   __syncthreads();
   const double sq = ((spart[0][lane] + spart[1][lane]) + spart[2][lane]) + spart[3][lane];
   const double lsum = log_tab(sq, lt);  // s >= 1 (the maximum term is exp(0))
-  if (SCDE_LPC_TW) __syncthreads();  // (region R becomes the transposes)
+  __syncthreads();  // (region R becomes the transposes)
   // pass 3: the row, its clamp, bounds and stores
   const bool want_maxi = a.maxi != nullptr;
   double bv = -INFINITY;
@@ -1151,7 +993,6 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
   };
   double bt = -INFINITY;
   for (int f0 = k0; f0 < k1r; f0 += kLpcFlush) {
-    double rg[kLpcFlush];  // the group's row values (SCDE_LPC_TW 0)
 #pragma unroll LPC_U3
     for (int kk = 0; kk < kLpcFlush; ++kk) {
       const int k = f0 + kk;
@@ -1166,11 +1007,11 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
         const bool tm = tiny || !(fabs(t1 - t2) > 37.5);
         r = hi - lsum;
         if (!(SCDE_LPC_DIAG & 4) && __builtin_amdgcn_ballot_w64(ok && tm)) {
-          double e = fma(lcf.y, E, LPC_EXP(fmax(t1, -746.0)));
+          double e = fma(lcf.y, E, exp_tab(fmax(t1, -746.0), etab));
           if (__builtin_amdgcn_ballot_w64(ok && tiny)) {
             // subnormal range: the Poisson term as the reference forms it, exp(log cfp_k + fp - maxp),
             // rounded once -- cfp_k E would carry the few bits a subnormal E has left
-            const double et = LPC_EXP(fmax((lcf.x + fp) - maxp, -746.0)) + LPC_EXP(fmax(t1, -746.0));
+            const double et = exp_tab(fmax((lcf.x + fp) - maxp, -746.0), etab) + exp_tab(fmax(t1, -746.0), etab);
             e = tiny ? et / sq : e;
           }
           const double rm = log_tab(e, lt) - (tiny ? 0.0 : lsum);
@@ -1196,25 +1037,11 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
           }
         }
       }
-      if (SCDE_LPC_TW)
-        tw[lane * kLpcTS + kk] = r;
-      else
-        rg[kk] = r;
-    }
-    if (!SCDE_LPC_TW && ok && !(SCDE_LPC_DIAG & 1)) {  // each lane its own column's 64 bytes
-      const long long off = (cbase + lane) * GS + f0;
-#pragma unroll
-      for (int i = 0; i < kLpcFlush / 2; ++i) {
-        if (T) tab_store2(T + off + 2 * i, rg[2 * i], rg[2 * i + 1], a.nt_rows);
-        if (D) {
-          const double2 bb = *reinterpret_cast<const double2*>(lds + kLpcBase + f0 + 2 * i);
-          tab_store2(D + off + 2 * i, rg[2 * i] - bb.x, rg[2 * i + 1] - bb.y, a.nt_rows);
-        }
-      }
+      tw[lane * kLpcTS + kk] = r;
     }
     // the flush: 4 lanes per column, 16 columns per store
 #pragma unroll
-    for (int i = 0; i < ((SCDE_LPC_DIAG & 1) || !SCDE_LPC_TW ? 0 : 4); ++i) {
+    for (int i = 0; i < ((SCDE_LPC_DIAG & 1) ? 0 : 4); ++i) {
       const int cc_ = i * 16 + (lane >> 2), kp = (lane & 3) * 2;
       if ((okm >> cc_) & 1ull) {
         const double r0 = tw[cc_ * kLpcTS + kp], r1 = tw[cc_ * kLpcTS + kp + 1];
@@ -1233,18 +1060,6 @@ __global__ __launch_bounds__(64 * kLpcWaves) void k_tables_lpc(TablesArgs a) {
   // the GPU suite stays green)
   const int GP = (SCDE_LPC_DIAG & 8) ? GS : min(GS, (G + 63) / 64 * 64);
   for (int f0 = Gr + kLpcFlush * w; f0 < GP; f0 += kLpcFlush * kLpcWaves) {
-    if (!SCDE_LPC_TW) {
-      if (ok) {
-        const long long off = (cbase + lane) * GS + f0;
-#pragma unroll
-        for (int i = 0; i < kLpcFlush / 2; ++i) {
-          const double z = ((SCDE_LPC_DIAG & 8) && f0 >= (G + 63) / 64 * 64) ? __builtin_nan("") : 0.0;
-          if (T) tab_store2(T + off + 2 * i, z, z, a.nt_rows);
-          if (D) tab_store2(D + off + 2 * i, z, z, a.nt_rows);
-        }
-      }
-      continue;
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int cc_ = i * 16 + (lane >> 2), kp = (lane & 3) * 2;
@@ -1328,138 +1143,6 @@ __global__ void k_base_cols(const int* __restrict__ ucl, const long long* __rest
     }
   }
   base_col[c] = bc;
-}
-
-// ELL rows: per gene the (cell, column) pairs of the cells whose column is not the cell's
-// baseline, in cell order, then pad entries (cell 0, the zero column) to a multiple of 8 plus
-// one look-ahead batch of 8 (k_boot2), or with padto 64 to whole 64-entry steps plus 8 (the tile
-// bootstrap's bounds).  A block takes 64 genes and every cell: each 64-cell step of uci (genes
-// fastest, as R lays out the count matrix) is read coalesced into an LDS tile (stride 65
-// against bank conflicts), then each wave compacts its genes' entries with ballots (mbcnt
-// prefix, cell order kept).  (A two-pass build over cell chunks, which fills the CUs a grid of
-// ngenes / 64 blocks leaves idle, was measured and lost.)  The block then writes the row
-// length, the pad entries and, with `key`, the gene's 16-bit tile-order key: the sum of its
-// entries' counts (ucl[col]) on a log scale -- genes of like expression next to each other, so
-// that waves in flight share columns -- under its gene chunk's index in the top bits (kch chunks
-// of the kgn genes, this launch's genes from kg0), descending when `desc` (heaviest genes first
-// within each chunk).  (Timing build SCDE_ELL_KEY_RANK: the sum of the count ranks, uci,
-// instead, no gather: the same bootstrap fetch, 28.5-28.6 GB per launch at config 4.)
-#ifndef SCDE_ELL_KEY_RANK
-#define SCDE_ELL_KEY_RANK 0
-#endif
-// waves per 64-gene block (4, 8 or 16).  8: blocks of 512 threads find room beside the tables
-// kernel's blocks (the ELL rows run on the aux stream during phase 2); measured against 16, one box,
-// alternating runs: shard of 8 device-resident 1.36-1.60 vs 1.43-1.46 ms, config 4 14.07-14.11 vs
-// 14.20-14.25, config 3 equal; 4 waves slower (config 3 6.77-6.93 vs 6.55-6.68 host -> host)
-#ifndef SCDE_ELL_WAVES
-#define SCDE_ELL_WAVES 8
-#endif
-constexpr int kEllWaves = SCDE_ELL_WAVES;
-constexpr int kEllKeyBits = 16;  // gene-order key width (launch_gene_order sorts these bits)
-__global__ __launch_bounds__(64 * kEllWaves) void k_ell(const int* __restrict__ uci, long long ld_uci, int ngenes,
-                                             int ncells, const long long* __restrict__ ucl_off,
-                                             const int* __restrict__ base_col, int stride, int pad_col,
-                                             int padto, int2* __restrict__ ent, int* __restrict__ nnz, int cell_off,
-                                             const int* __restrict__ ucl, unsigned* __restrict__ key,
-                                             int* __restrict__ idx, int kg0, int kgn, int kch, int desc) {
-  __shared__ int tile[64][65];  // [cell][gene]
-  // wid through readfirstlane: the wave's genes, rows and entry counts are then scalar values,
-  // which keeps the kernel at 6 or more waves per SIMD (as a vector value wid cost 95 VGPRs)
-  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g0 = blockIdx.x * 64;
-  constexpr int GPW = 64 / kEllWaves;  // genes per wave
-  const bool want_key = key != nullptr;
-  int n[GPW];
-  unsigned long long ks[GPW];  // per lane: its cells' kept counts (the key)
-#pragma unroll
-  for (int i = 0; i < GPW; ++i) {
-    n[i] = 0;
-    ks[i] = 0;
-  }
-  // software pipeline: the next 64-cell step's uci rows (this wave's 4 rows of the tile) and
-  // its lane cell's column offset and baseline column are loaded before the current step is
-  // compacted, so each step's loads wait behind the previous step's work, not in front of it
-  constexpr int RPW = 64 / kEllWaves;  // tile rows per wave
-  int pu[RPW];
-  long long poff = 0;
-  int pbc = -1;
-  auto prefetch = [&](int c0) {
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-      const int c = c0 + wid + r * kEllWaves, g = g0 + lane;
-      pu[r] = (c < ncells && g < ngenes) ? uci[(long long)g + ld_uci * c] : 0;
-    }
-    const int c = c0 + lane;
-    poff = 0;
-    pbc = -1;
-    if (c < ncells) {
-      poff = ucl_off[c];
-      pbc = base_col[c];
-    }
-  };
-  if (ncells > 0) prefetch(0);
-  for (int c0 = 0; c0 < ncells; c0 += 64) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) tile[wid + r * kEllWaves][lane] = pu[r];
-    const long long off = poff;
-    const int bc = pbc;
-    __syncthreads();
-    if (c0 + 64 < ncells) prefetch(c0 + 64);
-    const int c = c0 + lane;
-#pragma unroll
-    for (int i = 0; i < GPW; ++i) {
-      const int gl = wid * GPW + i, g = g0 + gl;
-      if (g >= ngenes) break;
-      int col = -1;
-      bool keep = false;
-      int rank = 0;
-      if (c < ncells) {
-        rank = tile[lane][gl];
-        col = (int)(off + rank);
-        keep = col != bc;
-      }
-      const unsigned long long m = __ballot(keep);
-      const int pos = n[i] + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-      if (keep) ent[(long long)g * stride + pos] = make_int2(c + cell_off, col);
-      if (want_key && keep) ks[i] += (unsigned)max(SCDE_ELL_KEY_RANK ? rank : ucl[col], 0);
-      n[i] += __popcll(m);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < GPW; ++i) {
-    const int g = g0 + wid * GPW + i;
-    if (g >= ngenes) break;
-    unsigned long long kv = ks[i];
-    if (want_key) {
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) kv += __shfl_xor(kv, o, 64);
-    }
-    const int nn = n[i];
-    if (lane == 0) {
-      nnz[g] = nn;
-      if (want_key) {
-        // the gene chunk of gene kg0 + g: chunk k holds [kgn k / kch, kgn (k + 1) / kch)
-        const long long gg = (long long)kg0 + g;
-        int k = (int)(gg * kch / kgn);
-        while (k + 1 < kch && (long long)kgn * (k + 1) / kch <= gg) ++k;
-        while (k > 0 && (long long)kgn * k / kch > gg) --k;
-        int hb = 0;  // bits of the chunk index
-        while ((1 << hb) < kch) ++hb;
-        // 16-bit keys (the sort then takes two radix passes, not four): the chunk index, then the
-        // count sum on a log scale, (2^(16 - hb) - 1) / 33 steps per octave
-        const unsigned vmax = (1u << (kEllKeyBits - hb)) - 1u;
-        unsigned v = (unsigned)(log2((double)kv + 1.0) * ((double)vmax / 33.0));
-        v = v > vmax ? vmax : v;
-        if (desc) v = vmax - v;
-        key[g] = (hb ? ((unsigned)k << (kEllKeyBits - hb)) : 0u) | v;
-        idx[g] = kg0 + g;
-      }
-    }
-    const int end = padto == 64 ? (nn > 0 ? (nn + 63) & ~63 : 64) + 8 : ((nn + 7) & ~7) + 8;
-    int2* E = ent + (long long)g * stride;
-    for (int q = nn + lane; q < end && q < stride; q += 64) E[q] = make_int2(0, pad_col);
-  }
 }
 
 // D[col] = T[col] - T[baseline column of its cell] (or T[col] when the cell has no
@@ -1561,220 +1244,6 @@ __global__ __launch_bounds__(256) void k_stretch_zu(const double* __restrict__ U
   if (t < kStretchSlots) ZU[((long long)set * Bp + b) * kStretchSlots + t] = part[0][t];
 }
 
-// ------------------------------------------------------------------ K2: bootstrap
-// Wave-level reduce-scatter of BC values: after it, lane l holds the value for
-// boot index (l >> (6 - log2 BC)) & (BC - 1) reduced over all 64 lanes.
-template <int BC, bool MAX>
-__device__ __forceinline__ double wave_reduce_scatter(double (&v)[BC], int lane) {
-  constexpr int L2 = (BC == 16) ? 4 : (BC == 8) ? 3 : (BC == 4) ? 2 : (BC == 2) ? 1 : 0;
-#pragma unroll
-  for (int s = 0; s < L2; ++s) {
-    const int half = BC >> (s + 1);
-    const int mask = 32 >> s;
-    const bool up = (lane & mask) != 0;
-#pragma unroll
-    for (int j = 0; j < half; ++j) {
-      // Both halves are read unconditionally first: a ternary over the array elements
-      // lets the optimizer merge the two reads into one lane-dependent index, which
-      // lowers to a compare/select chain over the whole register array.
-      const double lo = v[j], hi = v[j + half];
-      const double send = up ? lo : hi;
-      const double keep = up ? hi : lo;
-      const double r = __shfl_xor(send, mask, 64);
-      v[j] = MAX ? gt_max(keep, r) : keep + r;
-    }
-  }
-  double x = v[0];
-#pragma unroll
-  for (int mask = 32 >> L2; mask >= 1; mask >>= 1) {
-    const double r = __shfl_xor(x, mask, 64);
-    x = MAX ? gt_max(x, r) : x + r;
-  }
-  return x;
-}
-
-template <int BC, bool MAX>
-__device__ __forceinline__ void block_reduce_bc(double (&v)[BC], double* red, double* fin, int lane, int wid,
-                                                int nw) {
-  constexpr int L2 = (BC == 16) ? 4 : (BC == 8) ? 3 : (BC == 4) ? 2 : (BC == 2) ? 1 : 0;
-  static_assert(BC == 16 || BC == 8 || BC == 4 || BC == 2 || BC == 1, "BC must be a power of two <= 16");
-  const double x = wave_reduce_scatter<BC, MAX>(v, lane);
-  const int idx = (lane >> (6 - L2)) & (BC - 1);
-  if ((lane & ((64 >> L2) - 1)) == 0) red[wid * 16 + idx] = x;
-  __syncthreads();
-  if (threadIdx.x < BC) {
-    double r = red[threadIdx.x];
-    for (int w = 1; w < nw; ++w) r = MAX ? gt_max(r, red[w * 16 + threadIdx.x]) : r + red[w * 16 + threadIdx.x];
-    fin[threadIdx.x] = r;
-  }
-  __syncthreads();
-}
-
-template <int BC, int KPT>
-__device__ __forceinline__ void boot_pass(const BootArgs& a, int g, int b0, int n, const int2* __restrict__ E,
-                                          const double* __restrict__ W, const double* __restrict__ Zs,
-                                          double (&jpv)[KPT], double* red, double* fin, double* fin2) {
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6;
-  const int G = a.G, GS = a.GS;
-  double acc[KPT][BC];
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    const int k = tid + j * blockDim.x;
-#pragma unroll
-    for (int i = 0; i < BC; ++i) acc[j][i] = (Zs && k < G) ? Zs[(long long)(b0 + i) * GS + k] : 0.0;
-  }
-  const double* __restrict__ T = a.T;
-  for (int e = 0; e < n; ++e) {
-    const int2 en = E[e];
-    const int cell = __builtin_amdgcn_readfirstlane(en.x);
-    const int col = __builtin_amdgcn_readfirstlane(en.y);
-    const int bc = __builtin_amdgcn_readfirstlane(a.base_col ? a.base_col[cell] : -1);
-    const double* __restrict__ w = W + (long long)cell * a.Bp + b0;
-    double wv[BC];
-#pragma unroll
-    for (int i = 0; i < BC; ++i) wv[i] = w[i];
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) {
-      const int k = tid + j * blockDim.x;
-      if (k < G) {
-        double v = T[(long long)col * GS + k];
-        if (bc >= 0) v -= T[(long long)bc * GS + k];
-#pragma unroll
-        for (int i = 0; i < BC; ++i) acc[j][i] = fma(wv[i], v, acc[j][i]);
-      }
-    }
-  }
-  // ---- per-boot softmax over the grid (max, exp, sum) ----
-  double t[BC];
-#pragma unroll
-  for (int i = 0; i < BC; ++i) {
-    double m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (tid + j * (int)blockDim.x < G) m = gt_max(m, acc[j][i]);
-    t[i] = m;
-  }
-  block_reduce_bc<BC, true>(t, red, fin, lane, wid, nw);
-  double mx[BC];
-#pragma unroll
-  for (int i = 0; i < BC; ++i) mx[i] = fin[i];
-#pragma unroll
-  for (int i = 0; i < BC; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) {
-      const int k = tid + j * blockDim.x;
-      const double d = acc[j][i] - mx[i];
-      // exp(d) underflows to exactly 0 for d < -745.14; skip the call there
-      const double ev = (k < G && d >= -746.0) ? exp(d) : 0.0;
-      acc[j][i] = ev;
-      s += ev;
-    }
-    t[i] = s;
-  }
-  block_reduce_bc<BC, false>(t, red, fin2, lane, wid, nw);
-  if (tid < BC) {
-    const int b = b0 + tid;
-    const double m = mx[tid];
-    if (b < a.nboot && !(fabs(m) <= a.degen_thresh)) a.degen[g] = 1;
-    fin2[tid] = (b < a.nboot) ? 1.0 / (fin2[tid] * a.norm_mult) : 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < BC; ++i) {
-    const double r = fin2[i];
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) jpv[j] = fma(acc[j][i], r, jpv[j]);
-  }
-  __syncthreads();
-}
-
-template <int KPT>
-__global__ __launch_bounds__(1024) void k_boot(BootArgs a) {
-  __shared__ double red[16 * 16];
-  __shared__ double fin[16];
-  __shared__ double fin2[16];
-  const int tid = threadIdx.x;
-  for (int g = blockIdx.x; g < a.ngenes; g += gridDim.x) {
-    const int n = a.nnz[g];
-    const int2* E = a.ent + (long long)g * a.ent_stride;
-    const int set = a.wset ? a.wset[g] : 0;
-    const double* W = a.Wt + (long long)set * a.ncells * a.Bp;
-    const double* Zs = a.Z ? a.Z + (long long)set * a.Bp * a.GS : nullptr;
-    double jpv[KPT];
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) jpv[j] = 0.0;
-    int b0 = 0;
-    for (; b0 + 16 <= a.nboot; b0 += 16) boot_pass<16, KPT>(a, g, b0, n, E, W, Zs, jpv, red, fin, fin2);
-    if (a.nboot - b0 >= 8) {
-      boot_pass<8, KPT>(a, g, b0, n, E, W, Zs, jpv, red, fin, fin2);
-      b0 += 8;
-    }
-    if (a.nboot - b0 >= 4) {
-      boot_pass<4, KPT>(a, g, b0, n, E, W, Zs, jpv, red, fin, fin2);
-      b0 += 4;
-    }
-    if (a.nboot - b0 > 0) boot_pass<4, KPT>(a, g, b0, n, E, W, Zs, jpv, red, fin, fin2);
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) {
-      const int k = tid + j * blockDim.x;
-      if (k < a.G) a.out[(long long)g * a.out_g + (long long)k * a.out_k] = jpv[j];
-    }
-  }
-}
-
-// ------------------------------------------------------------------ K2 (fast path)
-// Cross-lane moves on VALU (no LDS path): gfx950 v_permlane{32,16}_swap exchange the
-// upper half-wave / odd rows of one register with the lower half / even rows of another;
-// DPP row_mirror (lane ^ 15), row_half_mirror (lane ^ 7), quad_perm (lane ^ 2, ^ 1).
-__device__ __forceinline__ void swap32(double& a, double& b) {
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false,
-                                                   false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false,
-                                                   false);
-  a = __hiloint2double((int)hi[0], (int)lo[0]);
-  b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ void swap16(double& a, double& b) {
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false,
-                                                   false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false,
-                                                   false);
-  a = __hiloint2double((int)hi[0], (int)lo[0]);
-  b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double x) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-constexpr int kDppMirror = 0x140, kDppHalfMirror = 0x141, kDppXor2 = 0x4E, kDppXor1 = 0xB1;
-// a double from the lane ds_swizzle's bit-mode PATTERN names (and 0x1F, xor in bits 10-14: within
-// 32 lanes; an LDS-crossbar op, no memory access)
-template <int PATTERN>
-__device__ __forceinline__ double swz_d(double x) {
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(x), PATTERN);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(x), PATTERN);
-  return __hiloint2double(hi, lo);
-}
-
-template <bool MAX>
-__device__ __forceinline__ double red_op(double a, double b) {
-  return MAX ? gt_max(a, b) : a + b;
-}
-
-// Sum over the 16 lanes of each row (16-lane group), the same bits on every lane of the row:
-// partners lane^1, lane^2 (quad_perm), lane^7 (row_half_mirror), lane^15 (row_mirror); each
-// step adds a pair of equal partial sums in both orders, and IEEE addition commutes.
-__device__ __forceinline__ double row16_sum(double v) {
-  v += dpp_d<kDppXor1>(v);
-  v += dpp_d<kDppXor2>(v);
-  v += dpp_d<kDppHalfMirror>(v);
-  v += dpp_d<kDppMirror>(v);
-  return v;
-}
-
 // Reduce-scatter of BC in {4, 8, 16} values over the wave, all on VALU.  Halving stages
 // pair lanes by bit 5, 4 (swaps: after the swap, a + b is the pair sum on every lane,
 // no selects), then bit 3 (lane ^ 15), bit 2 (lane ^ 7) with a keep/send select; the
@@ -1852,20 +1321,6 @@ __device__ __forceinline__ void block_reduce_all(const double (&x)[NB], bool liv
 // degenerate) |m - m'| <= 1, so the largest term is exp(m - m') in [1/e, e]: no overflow,
 // no loss, results equal to rounding.  Rows beyond 2^24 (including maxima below -FLT_MAX,
 // which convert to -inf) are flagged and recomputed in exact order by k_boot_exact.
-__device__ __forceinline__ void swap32f(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void swap16f(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xf, 0xf, true));
-}
 
 // f32 twin of wave_reduce_scatter_v (same lane -> index mapping), max only.
 template <int BC>
@@ -2053,9 +1508,6 @@ __global__ __launch_bounds__(64) void k_stretch_mask(const int2* __restrict__ en
 }
 
 constexpr double kBootExpCut = -50.0;  // k_boot2 softmax terms below e^-50 are dropped
-#ifndef SCDE_BOOT2_EXP_LINE
-#define SCDE_BOOT2_EXP_LINE 0
-#endif
 
 // One block per (gene, boot slab of NB).  Lanes over grid points (k = threadIdx.x,
 // G <= blockDim <= GS); NB bootstrap accumulators per lane in VGPRs.  Per ELL entry
@@ -2277,26 +1729,8 @@ __device__ __forceinline__ void boot2_slab(const double* __restrict__ D, const i
   // 1e-18 absolute floor of SURVEY 8(d)'s tolerance.  Rows are sharply peaked, so for most
   // (wave, boot) pairs no lane of the 64-point stretch is above the cut and the whole
   // wave skips the exp (a wave-uniform branch); inside an active wave the lanes below
-  // the cut are zeroed as before.
-#if SCDE_BOOT2_EXP_LINE
-  {  // study builds: one branch for the wave, the terms of all NB boots straight-line
-    bool any = false;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const double d = acc[i] - fm[i];
-      const bool need = live && d >= kBootExpCut;
-      any |= need;
-      acc[i] = need ? d : -1000.0;
-    }
-    if (__builtin_amdgcn_ballot_w64(any)) {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) acc[i] = exp_tab(acc[i], etab);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) acc[i] = 0.0;
-    }
-  }
-#else
+  // the cut are zeroed as before.  (k_boot_gene's form -- one branch per wave, all NB boots' terms
+  // straight-line -- was tried here as a study build and not kept.)
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
     const double d = acc[i] - fm[i];
@@ -2308,7 +1742,6 @@ __device__ __forceinline__ void boot2_slab(const double* __restrict__ D, const i
     else
       acc[i] = 0.0;
   }
-#endif
   if (diag & 8) {
     if (lane < NB) fm[lane] = acc[1];
   } else {
@@ -2977,7 +2410,6 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
   }
 }
 
-
 // ------------------------------------------------------------------ gene-block tile bootstrap
 // k_boot_gene: the tile bootstrap's first pass, one 4-wave block per (gene, group of up to SG
 // slabs).  At config 3 a slab needs about three of its thirteen 32-point bound tiles (DESIGN.md
@@ -3060,19 +2492,6 @@ __device__ __forceinline__ int pair_scatter_index(int m, int j) {
 }
 
 constexpr int kGeneSlabs = 8;     // slabs per group at most (K >= 2 rows each)
-#ifndef SCDE_GENE_EXP_BRANCH
-#define SCDE_GENE_EXP_BRANCH 0    // study builds: 1 = the round-5 per-boot branch around the exps
-#endif
-#ifndef SCDE_GENE_EXP
-#define SCDE_GENE_EXP 0           // study builds: 1 = exp_poly (no table), 2 = exp_tab with magic rounding
-#endif
-#if SCDE_GENE_EXP == 1
-#define GENE_EXP(d) exp_poly(d)
-#elif SCDE_GENE_EXP == 2
-#define GENE_EXP(d) exp_tab_m(d, etab)
-#else
-#define GENE_EXP(d) exp_tab(d, etab)
-#endif
 // WB waves per block: the launcher instantiates 4 only.  The kernel text still accepts 3 (12
 // rows for 5 slabs, for wide calls whose slabs mostly need two tiles): the fourth 32-boot bound
 // window is then split by entry chunks over the three waves (tile_bound_partial, exact int64
@@ -3342,25 +2761,8 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
   const int sqc = live ? sq : 0;
   // ---- 5. softmax terms, tile partial sums, jp partial rows.  The terms of all NB boots are one
   // straight-line block (no per-boot branch), so the compiler interleaves the NB x 2 independent
-  // exp chains instead of running each chain's latency alone.
-#if SCDE_GENE_EXP_BRANCH
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const double m = fmx[sqc][i];
-    const double d0 = a0[i] - m, d1 = a1[i] - m;
-    const bool n0 = mine && l0 && d0 >= kBootExpCut, n1 = mine && l1 && d1 >= kBootExpCut;
-    if (SCDE_TILE_DIAG & 4096) {
-      a0[i] = n0 ? d0 : 0.0;
-      a1[i] = n1 ? d1 : 0.0;
-    } else if (__builtin_amdgcn_ballot_w64(n0 || n1)) {
-      a0[i] = n0 ? exp_tab(d0, etab) : 0.0;
-      a1[i] = n1 ? exp_tab(d1, etab) : 0.0;
-    } else {
-      a0[i] = 0.0;
-      a1[i] = 0.0;
-    }
-  }
-#else
+  // exp chains instead of running each chain's latency alone.  The exps go through the LDS table
+  // (the table-free polynomial and a magic-number rounding variant were slower: DESIGN.md).
   {
     bool any = false;
 #pragma unroll
@@ -3376,15 +2778,14 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
     if (__builtin_amdgcn_ballot_w64(any)) {
 #pragma unroll
       for (int i = 0; i < NB; ++i) {
-        a0[i] = (SCDE_TILE_DIAG & 4096) ? a0[i] : GENE_EXP(a0[i]);
-        a1[i] = (SCDE_TILE_DIAG & 4096) ? a1[i] : GENE_EXP(a1[i]);
+        a0[i] = (SCDE_TILE_DIAG & 4096) ? a0[i] : exp_tab(a0[i], etab);
+        a1[i] = (SCDE_TILE_DIAG & 4096) ? a1[i] : exp_tab(a1[i], etab);
       }
     } else {
 #pragma unroll
       for (int i = 0; i < NB; ++i) a0[i] = a1[i] = 0.0;
     }
   }
-#endif
   {
     // quad partials: tsum[sum slot][quad][boot]
     double v[32];
@@ -3476,7 +2877,6 @@ __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(SCDE_TI
   }
 }
 
-
 #ifdef SCDE_TILE_TEST_WB1
 // hazard-test builds only (tests/test_kernel_resources.py), never run: one-wave blocks with a
 // token bound-staging area, whose LDS no longer caps occupancy at 4 waves per SIMD, so
@@ -3508,123 +2908,6 @@ __global__ void k_sum_partials(const double* __restrict__ part, long long part_s
   out[(long long)g * out_g + (long long)k * out_k] = s;
 }
 
-// ------------------------------------------------------------------ block reductions (simple)
-__device__ inline double block_max(double v, double* sh) {
-  v = wave_max(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int w = 1; w < nw; ++w) r = gt_max(r, sh[w]);
-  return r;
-}
-__device__ inline double block_sum(double v, double* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int w = 1; w < nw; ++w) r += sh[w];
-  return r;
-}
-
-// Reference-order fallback: tjp accumulated draw by draw exactly as
-// src/jpmatLogBoot.cpp:251-270 does, for genes flagged degenerate by k_boot.
-template <int KPT>
-__global__ __launch_bounds__(1024) void k_boot_exact(ExactArgs a) {
-  __shared__ double sh[16];
-  const int g = blockIdx.x + a.g_lo;
-  if (!a.degen[g]) return;
-  const int tid = threadIdx.x;
-  const int set = a.wset ? a.wset[g] : 0;
-  const int* dr = a.draws + (long long)set * a.nboot * a.ndraw;
-  double jpv[KPT];
-  for (int j = 0; j < KPT; ++j) jpv[j] = 0.0;
-  for (int b = 0; b < a.nboot; ++b) {
-    double t[KPT];
-    for (int j = 0; j < KPT; ++j) t[j] = 0.0;
-    const long long gu = a.gene_mod > 0 ? g % a.gene_mod : g;  // fused groups: the gene's uci row
-    for (int d = 0; d < a.ndraw; ++d) {
-      const int cell = dr[(long long)b * a.ndraw + d];
-      if (cell < 0) continue;  // the shorter fused group's padding (uniform over the block)
-      long long col;
-      if (a.uci)
-        col = a.ucl_off[cell] + a.uci[gu + a.ld_uci * cell];
-      else
-        col = (long long)cell * a.ngenes + g;  // jpmat layout: matrix-major rows
-      // fused tables: T = D + D[baseline column] (<= 1 ulp of T; clamped values exact)
-      const int bc = a.base_col ? a.base_col[cell] : -1;
-      const double* base = (bc >= 0 && bc != col) ? a.T + (long long)bc * a.GS : nullptr;
-      for (int j = 0; j < KPT; ++j) {
-        const int k = tid + j * blockDim.x;
-        if (k < a.G) {
-          const double tv = base ? __dadd_rn(a.T[col * a.GS + k], base[k]) : a.T[col * a.GS + k];
-          t[j] = __dadd_rn(t[j], tv);
-        }
-      }
-    }
-    double m = -INFINITY;
-    for (int j = 0; j < KPT; ++j)
-      if (tid + j * (int)blockDim.x < a.G) m = gt_max(m, t[j]);
-    m = block_max(m, sh);
-    double s = 0.0;
-    for (int j = 0; j < KPT; ++j) {
-      const int k = tid + j * blockDim.x;
-      t[j] = (k < a.G) ? exp(t[j] - m) : 0.0;
-      s += t[j];
-    }
-    s = block_sum(s, sh);
-    const double den = s * a.norm_mult;
-    for (int j = 0; j < KPT; ++j) jpv[j] += t[j] / den;
-  }
-  for (int j = 0; j < KPT; ++j) {
-    const int k = tid + j * blockDim.x;
-    if (k < a.G) a.out[(long long)g * a.out_g + (long long)k * a.out_k] = jpv[j];
-  }
-}
-
-// nboot == 0 (src/jpmatLogBoot.cpp:237-248): sum over cells in order, softmax.
-template <int KPT>
-__global__ __launch_bounds__(1024) void k_noboot(NoBootArgs a) {
-  __shared__ double sh[16];
-  const int g = blockIdx.x, tid = threadIdx.x;
-  double t[KPT];
-  for (int j = 0; j < KPT; ++j) t[j] = 0.0;
-  for (int c = 0; c < a.ncells; ++c) {
-    const long long col = a.ucl_off[c] + a.uci[(long long)g + a.ld_uci * c];
-    const double* src = a.T + col * a.GS;
-    for (int j = 0; j < KPT; ++j) {
-      const int k = tid + j * blockDim.x;
-      if (k < a.G) t[j] = __dadd_rn(t[j], src[k]);
-    }
-  }
-  if (a.ensemble) {
-    double s = 0.0;
-    for (int j = 0; j < KPT; ++j) s += (tid + j * (int)blockDim.x < a.G) ? t[j] : 0.0;
-    s = block_sum(s, sh);
-    for (int j = 0; j < KPT; ++j) t[j] = t[j] / s;
-  } else {
-    double m = -INFINITY;
-    for (int j = 0; j < KPT; ++j)
-      if (tid + j * (int)blockDim.x < a.G) m = gt_max(m, t[j]);
-    m = block_max(m, sh);
-    double s = 0.0;
-    for (int j = 0; j < KPT; ++j) {
-      const int k = tid + j * blockDim.x;
-      t[j] = (k < a.G) ? exp(t[j] - m) : 0.0;
-      s += t[j];
-    }
-    s = block_sum(s, sh);
-    for (int j = 0; j < KPT; ++j) t[j] = t[j] / s;
-  }
-  for (int j = 0; j < KPT; ++j) {
-    const int k = tid + j * blockDim.x;
-    if (k < a.G) a.out[(long long)g * a.out_g + (long long)k * a.out_k] = t[j];
-  }
-}
-
 // ensemble: E = exp(T) / colsum(exp(T)) per column (src/jpmatLogBoot.cpp:226-229)
 __global__ __launch_bounds__(256) void k_ensemble_cols(const double* __restrict__ T, long long ncols, int G, int GS,
                                                        double* __restrict__ Eo) {
@@ -3637,619 +2920,7 @@ __global__ __launch_bounds__(256) void k_ensemble_cols(const double* __restrict_
   for (int k = lane; k < G; k += 64) Eo[col * GS + k] = exp(T[col * GS + k]) / s;
 }
 
-// ------------------------------------------------------------------ modes / post gathers
-__global__ void k_modes(const int* __restrict__ uci, long long ld_uci, int ngenes, int ncells,
-                        const long long* __restrict__ ucl_off, const int* __restrict__ maxi,
-                        const double* __restrict__ mag, double* __restrict__ modes, long long mg, long long mc) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)ngenes * ncells) return;
-  const int g = (int)(i % ngenes), c = (int)(i / ngenes);
-  const long long col = ucl_off[c] + uci[(long long)g + ld_uci * c];
-  modes[g * mg + c * mc] = mag[maxi[col]];
-}
-
-__global__ void k_post(const int* __restrict__ uci, long long ld_uci, int ngenes, int c,
-                       const long long* __restrict__ ucl_off, const double* __restrict__ T, int G, int GS,
-                       double* __restrict__ post, long long pg, long long pk) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)ngenes * G) return;
-  const int g = (int)(i % ngenes), k = (int)(i / ngenes);
-  const long long col = ucl_off[c] + uci[(long long)g + ld_uci * c];
-  post[g * pg + k * pk] = T[col * GS + k];
-}
-
-// ------------------------------------------------------------------ device unique-count builder
-// counts: column-major, column = cellidx[c], rows g0 .. g0+ngenes
-__global__ void k_cell_minmax(const int* __restrict__ counts, long long ld, long long g0, int ngenes,
-                              const int* __restrict__ cellidx, int* __restrict__ cmax, int* __restrict__ cmin) {
-  __shared__ int smax[16], smin[16];
-  const int c = blockIdx.x;
-  const int* col = counts + (long long)cellidx[c] * ld + g0;
-  int mx = 0, mn = 0x7fffffff;
-  // 16-byte loads over the aligned middle of the column (one count matrix pass, HBM-bound)
-  const int head = (int)min<long long>(ngenes, (4 - (((uintptr_t)col >> 2) & 3)) & 3);
-  const int nv = (ngenes - head) >> 2;
-  const int4* col4 = reinterpret_cast<const int4*>(col + head);
-  for (int i = threadIdx.x; i < nv; i += blockDim.x) {
-    const int4 x = col4[i];
-    mx = max(mx, max(max(x.x, x.y), max(x.z, x.w)));
-    mn = min(mn, min(min(x.x, x.y), min(x.z, x.w)));
-  }
-  for (int g = threadIdx.x; g < head; g += blockDim.x) {
-    mx = max(mx, col[g]);
-    mn = min(mn, col[g]);
-  }
-  for (int g = head + 4 * nv + threadIdx.x; g < ngenes; g += blockDim.x) {
-    mx = max(mx, col[g]);
-    mn = min(mn, col[g]);
-  }
-  for (int m = 32; m >= 1; m >>= 1) {
-    mx = max(mx, __shfl_xor(mx, m, 64));
-    mn = min(mn, __shfl_xor(mn, m, 64));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    smax[threadIdx.x >> 6] = mx;
-    smin[threadIdx.x >> 6] = mn;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
-      mx = max(mx, smax[w]);
-      mn = min(mn, smin[w]);
-    }
-    mx = max(mx, smax[0]);
-    mn = min(mn, smin[0]);
-    cmax[c] = mx;
-    cmin[c] = mn;
-  }
-}
-
-// One cell per blockIdx.y, KM genes per thread.  Counts below 64*MW set bits in an LDS
-// copy of the cell's first MW bitmap words (most counts are small, and 0 alone is ~2/3 of
-// them: global atomics on that one word serialised at L2); the block then flushes at most
-// MW global atomicOr.  Larger counts go straight to global memory (sparse words).
-template <int KM, int MW>
-__global__ __launch_bounds__(256) void k_mark(const int* __restrict__ counts, long long ld, long long g0,
-                                              int ngenes, const int* __restrict__ cellidx,
-                                              const long long* __restrict__ woff,
-                                              unsigned long long* __restrict__ bits, int* __restrict__ flags) {
-  __shared__ unsigned long long lw[MW];
-  const int c = blockIdx.y;
-  if (threadIdx.x < MW) lw[threadIdx.x] = 0ull;
-  __syncthreads();
-  const int* __restrict__ col = counts + (long long)cellidx[c] * ld + g0;
-  unsigned long long* __restrict__ cb = bits + woff[c];
-  // flags (fixed-width bitmaps, cmax unknown): bit 0 a negative count, bit 1 a count past the
-  // cell's bitmap (the caller rebuilds with exact widths); such counts are not marked
-  const long long width = flags ? woff[c + 1] - woff[c] : 0;
-  const int base = blockIdx.x * (256 * KM) + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < KM; ++j) {
-    const int g = base + j * 256;
-    bool valid = g < ngenes;
-    const int x = valid ? col[g] : 0;
-    if (flags && valid && (x < 0 || (x >> 6) >= width)) {
-      atomicOr(flags, x < 0 ? 1 : 2);
-      valid = false;
-    }
-    // count 0 (the common case) by ballot: one LDS atomic per wave instead of up to 64
-    if (__ballot(valid && x == 0) && (threadIdx.x & 63) == 0) atomicOr(&lw[0], 1ull);
-    if (valid && x != 0) {
-      const unsigned long long bit = 1ull << (x & 63);
-      if ((x >> 6) < MW)
-        atomicOr(&lw[x >> 6], bit);
-      else
-        atomicOr(&cb[x >> 6], bit);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < MW) {
-    const unsigned long long v = lw[threadIdx.x];
-    // words beyond the cell's own bitmap are never set (x <= cmax)
-    if (v) atomicOr(&cb[threadIdx.x], v);
-  }
-}
-
-// per cell: exclusive popcount prefix of its bitmap words -> rank, and #unique
-__global__ __launch_bounds__(256) void k_rank(const unsigned long long* __restrict__ bits,
-                                              const long long* __restrict__ woff, int* __restrict__ rank,
-                                              int* __restrict__ nuniq, const int* __restrict__ flags_in,
-                                              int* __restrict__ flags_out) {
-  __shared__ int wsum[4];
-  __shared__ int carry;
-  const int c = blockIdx.x;
-  const long long w0 = woff[c], w1 = woff[c + 1];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (long long base = w0; base < w1; base += blockDim.x) {
-    const long long w = base + threadIdx.x;
-    const int pc = (w < w1) ? __popcll(bits[w]) : 0;
-    int incl = pc;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    int pre = carry;
-    for (int v = 0; v < wid; ++v) pre += wsum[v];
-    if (w < w1) rank[w] = pre + incl - pc;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) nuniq[c] = carry;
-  // k_mark's flags next to the counts (one read-back for both; k_mark ran before in stream order)
-  if (flags_in && c == 0 && threadIdx.x == 0) *flags_out = *flags_in;
-}
-
-__global__ __launch_bounds__(256) void k_fill_ucl(const unsigned long long* __restrict__ bits,
-                                                  const long long* __restrict__ woff,
-                                                  const int* __restrict__ rank,
-                                                  const long long* __restrict__ ucl_off, int* __restrict__ ucl) {
-  const int c = blockIdx.x;
-  const long long w0 = woff[c], w1 = woff[c + 1];
-  for (long long w = w0 + threadIdx.x; w < w1; w += blockDim.x) {
-    unsigned long long b = bits[w];
-    long long pos = ucl_off[c] + rank[w];
-    while (b) {
-      const int t = __ffsll((long long)b) - 1;
-      ucl[pos++] = (int)((w - w0) * 64 + t);
-      b &= b - 1;
-    }
-  }
-}
-
-__global__ void k_uci(const int* __restrict__ counts, long long ld, long long g0, int ngenes, int ncells,
-                      const int* __restrict__ cellidx, const long long* __restrict__ woff,
-                      const unsigned long long* __restrict__ bits, const int* __restrict__ rank,
-                      int* __restrict__ uci) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)ngenes * ncells) return;
-  const int g = (int)(i % ngenes), c = (int)(i / ngenes);
-  const int x = counts[(long long)cellidx[c] * ld + g0 + g];
-  const long long w = woff[c] + (x >> 6);
-  const unsigned long long below = bits[w] & ((1ull << (x & 63)) - 1ull);
-  uci[(long long)g + (long long)ngenes * c] = rank[w] + __popcll(below);
-}
-
-// ------------------------------------------------------------------ jpmat: transpose column-major -> row-major
-__global__ void k_colmajor_to_rows(const double* __restrict__ src, int nrows, int ncols, int GS,
-                                   double* __restrict__ dst) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)nrows * ncols) return;
-  const int r = (int)(i % nrows), k = (int)(i / nrows);
-  dst[(long long)r * GS + k] = src[i];
-}
-
-// ------------------------------------------------------------------ K3 helpers
-// matSlideMult (src/matSlideMult.cpp:12-20) for R adjacent outputs starting at shift s0:
-// X[s] = sum_t A[t + max(s,0)] * B[t + max(-s,0)], t ascending, each product and sum
-// rounded separately.  A and B are zero-padded by >= R entries past n, so the R sums can
-// all run to the longest one (a padded term adds +0 to a non-negative sum: bit-identical).
-// One sliding register window and one shared operand feed R independent sums per step;
-// LDS reads are issued 4 steps at a time.
-template <int R>
-__device__ __forceinline__ void slide_group(const double* __restrict__ A, const double* __restrict__ B, int n,
-                                            int s0, double (&c)[R]) {
-#pragma unroll
-  for (int r = 0; r < R; ++r) c[r] = 0.0;
-  double w[R];
-  if (s0 >= 0) {
-    // output r: sum_{t < n-s0-r} A[t+s0+r] B[t]; longest is r = 0
-#pragma unroll
-    for (int r = 0; r < R; ++r) w[r] = A[s0 + r];
-    const int len = n - s0;
-    auto step = [&](double b, double anew) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) c[r] = __dadd_rn(c[r], __dmul_rn(w[r], b));
-#pragma unroll
-      for (int r = 0; r + 1 < R; ++r) w[r] = w[r + 1];
-      w[R - 1] = anew;
-    };
-    int t = 0;
-    for (; t + 4 <= len; t += 4) {
-      const double b0 = B[t], b1 = B[t + 1], b2 = B[t + 2], b3 = B[t + 3];
-      const double a0 = A[t + s0 + R], a1 = A[t + s0 + R + 1], a2 = A[t + s0 + R + 2], a3 = A[t + s0 + R + 3];
-      step(b0, a0);
-      step(b1, a1);
-      step(b2, a2);
-      step(b3, a3);
-    }
-    for (; t < len; ++t) step(B[t], A[t + s0 + R]);
-  } else if (s0 + R - 1 < 0) {
-    // output r: sum_{t < n+s0+r} A[t] B[t-s0-r]; longest is r = R-1
-#pragma unroll
-    for (int r = 0; r < R; ++r) w[r] = B[-s0 - r];
-    const int len = n + s0 + R - 1;
-    auto step = [&](double av, double bnew) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) c[r] = __dadd_rn(c[r], __dmul_rn(av, w[r]));
-#pragma unroll
-      for (int r = R - 1; r > 0; --r) w[r] = w[r - 1];
-      w[0] = bnew;
-    };
-    int t = 0;
-    for (; t + 4 <= len; t += 4) {
-      const double a0 = A[t], a1 = A[t + 1], a2 = A[t + 2], a3 = A[t + 3];
-      const double b1 = B[t + 1 - s0], b2 = B[t + 2 - s0], b3 = B[t + 3 - s0], b4 = B[t + 4 - s0];
-      step(a0, b1);
-      step(a1, b2);
-      step(a2, b3);
-      step(a3, b4);
-    }
-    for (; t < len; ++t) step(A[t], B[t + 1 - s0]);
-  } else {
-    // the group that straddles s = 0: one output at a time
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int s = s0 + r;
-      const int o1 = s > 0 ? s : 0, o2 = s < 0 ? -s : 0;
-      const int len = n - (s < 0 ? -s : s);
-      double acc = 0.0;
-      for (int t = 0; t < len; ++t) acc = __dadd_rn(acc, __dmul_rn(A[t + o1], B[t + o2]));
-      c[r] = acc;
-    }
-  }
-}
-
-// Both sides of the slide in one form: X(d) = sum_t P[t] Q[t + d], t ascending, for R
-// adjacent lags d = d0 .. d0+R-1 (s >= 0: P = B, Q = A, d = s; s < 0: P = A, Q = B,
-// d = -s), so every lane runs the same instruction stream whichever side its group is on.
-// Products are commutative and the terms are summed in the same t order as above:
-// bit-identical to slide_group.  Q is zero-padded by >= R past n.
-template <int R>
-__device__ __forceinline__ void slide_lags(const double* P, const double* Q0, const double* Q1, int n, int d0,
-                                           double (&c)[R], int pl = 0, int ph = 1 << 30, int ql = 0,
-                                           int qh = 1 << 30) {
-  // P is 16-B aligned and t steps by 4: P[t..t+3] is two aligned 16-B reads.  Q0 / Q1 hold
-  // the row at an even / odd double offset; the one matching the parity of d0 + R puts
-  // Q[t + d0 + R] on a 16-B boundary (ds_read_b128: 16 B per lane in 4 LDS cycles, where
-  // ds_read2_b64 takes 16).
-  const double* Q = ((d0 + R) & 1) ? Q1 : Q0;
-  // Support restriction (bit-identical): a term P[t] Q[t + d] with P[t] == 0 or Q[t + d] ==
-  // 0 is +0 (both rows are finite and >= 0; the caller passes full ranges otherwise), and
-  // adding +0 to a non-negative partial sum changes nothing, so t only needs to cover
-  // [pl, ph] (P nonzero) intersected with the t where some lag's Q[t + d] is nonzero,
-  // starting on a multiple of 4 so the aligned reads stay aligned.
-  const int tlo = max(max(0, pl), ql - d0 - R + 1);
-  const int tend0 = min(min(n - d0, ph + 1), qh - d0 + 1);
-  const bool any = tlo < tend0;  // else every term is +0 and so is every sum
-  const int t0 = any ? (tlo & ~3) : 0;
-  const int tend = any ? tend0 : 0;
-  double w[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    c[r] = 0.0;
-    w[r] = Q[t0 + d0 + r];
-  }
-  const int len = tend;
-  auto step = [&](double p, double qnew) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) c[r] = __dadd_rn(c[r], __dmul_rn(w[r], p));
-#pragma unroll
-    for (int r = 0; r + 1 < R; ++r) w[r] = w[r + 1];
-    w[R - 1] = qnew;
-  };
-  int t = t0;
-  for (; t + 4 <= len; t += 4) {
-    const double2 pa = *reinterpret_cast<const double2*>(P + t);
-    const double2 pb = *reinterpret_cast<const double2*>(P + t + 2);
-    const double2 qa = *reinterpret_cast<const double2*>(Q + t + d0 + R);
-    const double2 qb = *reinterpret_cast<const double2*>(Q + t + d0 + R + 2);
-    step(pa.x, qa.x);
-    step(pa.y, qa.y);
-    step(pb.x, qb.x);
-    step(pb.y, qb.y);
-  }
-  for (; t < len; ++t) step(P[t], Q[t + d0 + R]);
-}
-
-// ------------------------------------------------------------------ K3: ratio posterior + summary
-template <int R>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCDE_RATIO_WPE))) void k_ratio_summary(RatioArgs a) {
-  // All LDS is in the dynamic region, every array at a 16-B aligned offset (a static
-  // __shared__ in front would shift the base, and misaligned 16-B reads replay):
-  //   A, B        the prior-weighted rows at even double offsets, zero-padded to NA >= n + 8
-  //               (the sliding windows read past the end; a padded term adds +0 to a
-  //               non-negative sum: bit-identical);
-  //   A1, B1      the same rows at odd offsets: one of Q / Q1 puts a lane's window on a
-  //               16-B boundary, so every slide read is a ds_read_b128;
-  //   X           the 2n-1 outputs + 48 doubles of per-wave scratch;
-  //   red, red2   8 doubles each; ired, ired2, ired3 8 ints each.
-  extern __shared__ __attribute__((aligned(16))) double sh[];
-  const int n = a.n, m = 2 * a.n - 1;
-  const int NA = (n + 9) & ~1;
-  double* A = sh;
-  double* B = sh + NA;
-  double* A1 = sh + 2 * NA + 1;
-  double* B1 = sh + 3 * NA + 1;
-  double* X = sh + 4 * NA + 2;
-  double* red = X + ((m + 49) & ~1);
-  double* red2 = red + 8;
-  int* ired = reinterpret_cast<int*>(red2 + 8);
-  int* ired2 = ired + 8;
-  int* ired3 = ired + 16;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6;
-  // Output groups q (R adjacent lags each): s0 = R q - (n-1) >= 0 ("pos": P = B, Q = A),
-  // s0 + R - 1 < 0 ("neg": P = A, Q = B), else the one group straddling s = 0.  Each
-  // side's groups go to its own waves (the shared operand P[t] is then one address per
-  // wave, a broadcast), longest first, so a wave's lanes run similar lengths.
-  const int NQ = (m + R - 1) / R;
-  const int qpos0 = (n - 1 + R - 1) / R;           // first pos group
-  const int NPOS = NQ - qpos0;
-  const int NNEG = n > R ? (n - R - 1) / R + 1 : 0;  // groups q < qneg0 with R q + R - 1 < n - 1
-  const int NSTR = qpos0 - NNEG;                     // 0 or 1
-  int* sup = ired + 24;  // [pl, ph, ql, qh, nonfinite] of the current gene's rows
-  for (int g = blockIdx.x; g < a.ngenes; g += gridDim.x) {
-    if (tid == 0) {
-      sup[0] = 1 << 30;
-      sup[1] = -1;
-      sup[2] = 1 << 30;
-      sup[3] = -1;
-      sup[4] = 0;
-    }
-    __syncthreads();
-    for (int k = tid; k < NA && !a.xin; k += blockDim.x) {
-      double va = 0.0, vb = 0.0;
-      if (k < n) {
-        const double y = a.prior_y ? a.prior_y[k] : 1.0;
-        const double p1 = a.jp1[(long long)g * a.j1g + (long long)k * a.j1k];
-        const double p2 = a.jp2[(long long)g * a.j2g + (long long)k * a.j2k];
-        va = a.prior_y ? __dmul_rn(p1, y) : p1;
-        vb = a.prior_y ? __dmul_rn(p2, y) : p2;
-      }
-      A[k] = va;
-      B[k] = vb;
-      A1[k] = va;
-      B1[k] = vb;
-      if (k < n) {
-        // supports of the two rows (nonzero entries); any non-finite value turns the
-        // restriction off (0 * inf is not +0)
-        if (va != 0.0) {
-          atomicMin(&sup[0], k);
-          atomicMax(&sup[1], k);
-        }
-        if (vb != 0.0) {
-          atomicMin(&sup[2], k);
-          atomicMax(&sup[3], k);
-        }
-        if (!isfinite(va) || !isfinite(vb) || va < 0.0 || vb < 0.0) sup[4] = 1;
-      }
-    }
-    __syncthreads();
-    int al = 0, ah = 1 << 30, bl = 0, bh = 1 << 30;
-    if (!a.xin && !sup[4]) {
-      al = sup[0];
-      ah = sup[1];
-      bl = sup[2];
-      bh = sup[3];
-    }
-    // matSlideMult (src/matSlideMult.cpp:12-20): X[o] = sum_t A[t + max(s,0)] * B[t + max(-s,0)],
-    // s = o - (n-1), t ascending, each product and sum rounded separately.
-    dd ls = {0.0, 0.0};
-    for (int o = tid; o < m && a.xin; o += blockDim.x) X[o] = a.xin[(long long)g * a.xg + (long long)o * a.xo];
-    if (!a.xin && !(SCDE_RATIO_DIAG & 1)) {
-      const int side = nw >= 2 ? (wid & 1) : 0;
-      const int wstep = nw >= 2 ? 64 * (nw >> 1) : 64;
-      for (int pass = 0; pass < (nw >= 2 ? 1 : 2); ++pass) {
-        const int sd = nw >= 2 ? side : pass;
-        const int cnt = sd == 0 ? NPOS : NNEG + NSTR;
-        for (int i = (nw >= 2 ? (wid >> 1) * 64 : 0) + lane; i < cnt; i += wstep) {
-          double c[R];
-          if (sd == 0) {  // pos, longest first: q = qpos0 + i, lags d = s0 .. s0 + R - 1
-            const int q = qpos0 + i, o0 = R * q, s0 = o0 - (n - 1);
-            slide_lags<R>(B, A, A1, n, s0, c, bl, bh, al, ah);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-              if (o0 + r < m) {
-                X[o0 + r] = c[r];
-                ls = dd_add_d(ls, c[r]);
-              }
-            }
-          } else if (i < NNEG) {  // neg, longest first: q = NNEG - 1 - i, lags -s0 - R + 1 ..
-            const int q = NNEG - 1 - i, o0 = R * q, s0 = o0 - (n - 1);
-            slide_lags<R>(A, B, B1, n, -s0 - R + 1, c, al, ah, bl, bh);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-              const int o = o0 + R - 1 - r;
-              X[o] = c[r];
-              ls = dd_add_d(ls, c[r]);
-            }
-          } else {  // the group straddling s = 0 (only when (n - 1) % R != 0)
-            const int q = NNEG, o0 = R * q;
-            slide_group<R>(A, B, n, o0 - (n - 1), c);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-              if (o0 + r < m) {
-                X[o0 + r] = c[r];
-                ls = dd_add_d(ls, c[r]);
-              }
-            }
-          }
-        }
-      }
-    }
-    // row sum (R rowSums accumulates in long double): double-double block reduce
-    for (int d = 32; d >= 1; d >>= 1) {
-      dd o2;
-      o2.hi = __shfl_xor(ls.hi, d, 64);
-      o2.lo = __shfl_xor(ls.lo, d, 64);
-      ls = dd_add(ls, o2);
-    }
-    if (lane == 0) {
-      red[wid] = ls.hi;
-      red2[wid] = ls.lo;
-    }
-    __syncthreads();
-    dd tot = {red[0], red2[0]};
-    for (int w = 1; w < nw; ++w) tot = dd_add(tot, dd{red[w], red2[w]});
-    const bool norm = a.normalize && !a.xin;
-    const double rs = norm ? dd_to_d(tot) : 1.0;
-    __syncthreads();
-    for (int o = tid; o < m; o += blockDim.x) {
-      const double p = norm ? X[o] / rs : X[o];
-      X[o] = p;
-      if (a.ratio) a.ratio[(long long)g * a.rg + (long long)o * a.ro] = p;
-    }
-    __syncthreads();
-    if (!a.res || (SCDE_RATIO_DIAG & 2)) continue;
-    // ---- quick.distribution.summary: contiguous chunk per thread ----
-    const int per = (m + blockDim.x - 1) / blockDim.x;
-    const int c0 = tid * per, c1 = min(m, c0 + per);
-    dd csum = {0.0, 0.0}, zsum = {0.0, 0.0};
-    double bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int o = c0; o < c1; ++o) {
-      const double p = X[o];
-      csum = dd_add_d(csum, p);
-      zsum = dd_add_d(zsum, p + 1e-15);
-      if (p > bv) {
-        bv = p;
-        bi = o;
-      }
-    }
-    // block scan of chunk sums (dd): inclusive within the wave, then exclusive
-    dd incl = csum;
-    for (int d = 1; d < 64; d <<= 1) {
-      dd o2;
-      o2.hi = __shfl_up(incl.hi, d, 64);
-      o2.lo = __shfl_up(incl.lo, d, 64);
-      if (lane >= d) incl = dd_add(o2, incl);
-    }
-    dd excl;
-    excl.hi = __shfl_up(incl.hi, 1, 64);
-    excl.lo = __shfl_up(incl.lo, 1, 64);
-    if (lane == 0) excl = dd{0.0, 0.0};
-    // argmax (first max)
-    for (int d = 32; d >= 1; d >>= 1) {
-      const double ov = __shfl_xor(bv, d, 64);
-      const int oi = __shfl_xor(bi, d, 64);
-      if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    // z-sum total
-    dd zt = zsum;
-    for (int d = 32; d >= 1; d >>= 1) {
-      dd o2;
-      o2.hi = __shfl_xor(zt.hi, d, 64);
-      o2.lo = __shfl_xor(zt.lo, d, 64);
-      zt = dd_add(zt, o2);
-    }
-    __syncthreads();
-    if (lane == 63) {
-      red[wid] = incl.hi;
-      red2[wid] = incl.lo;
-    }
-    if (lane == 0) {
-      ired[wid] = bi;
-      X[m + wid] = bv;  // scratch after the row (allocated)
-      X[m + 8 + wid] = zt.hi;
-      X[m + 16 + wid] = zt.lo;
-    }
-    __syncthreads();
-    dd pre = {0.0, 0.0};
-    for (int w = 0; w < wid; ++w) pre = dd_add(pre, dd{red[w], red2[w]});
-    dd run = dd_add(pre, excl);
-    // walk chunk: lb = last o with cs < 0.025, ub = first o with cs > 0.975
-    int lbi = -1, ubi = 0x7fffffff;
-    for (int o = c0; o < c1; ++o) {
-      run = dd_add_d(run, X[o]);
-      const double cs = dd_to_d(run);
-      if (cs < 0.025) lbi = o;
-      if (cs > (1 - 0.025) && ubi == 0x7fffffff) ubi = o;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-      lbi = max(lbi, __shfl_xor(lbi, d, 64));
-      ubi = min(ubi, __shfl_xor(ubi, d, 64));
-    }
-    __syncthreads();
-    if (lane == 0) {
-      ired2[wid] = lbi;
-      ired3[wid] = ubi;
-    }
-    __syncthreads();
-    // Z (R/functions.R:3514-3531): rpost = (p + 1e-15) / rowSums(p + 1e-15);
-    // gs = sum(rpost[1:(zi-1)]) (R's 1:0 selects column 1 when zi is the first column),
-    // as a block-parallel double-double sum over each thread's chunk.
-    dd zt2 = {X[m + 8], X[m + 16]};
-    for (int w = 1; w < nw; ++w) zt2 = dd_add(zt2, dd{X[m + 8 + w], X[m + 16 + w]});
-    const double rs2 = dd_to_d(zt2);
-    const int zend = a.zi == 0 ? 1 : a.zi;
-    dd gp = {0.0, 0.0};
-    for (int o = c0; o < min(c1, zend); ++o) gp = dd_add_d(gp, (X[o] + 1e-15) / rs2);
-    for (int d = 32; d >= 1; d >>= 1) {
-      dd o2;
-      o2.hi = __shfl_xor(gp.hi, d, 64);
-      o2.lo = __shfl_xor(gp.lo, d, 64);
-      gp = dd_add(gp, o2);
-    }
-    if (lane == 0) {
-      X[m + 24 + wid] = gp.hi;
-      X[m + 32 + wid] = gp.lo;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int lb = ired2[0], ub = ired3[0];
-      double mb = X[m];
-      int mi = ired[0];
-      dd gs = {X[m + 24], X[m + 32]};
-      for (int w = 1; w < nw; ++w) {
-        lb = max(lb, ired2[w]);
-        ub = min(ub, ired3[w]);
-        const double v = X[m + w];
-        if (v > mb || (v == mb && ired[w] < mi)) {
-          mb = v;
-          mi = ired[w];
-        }
-        gs = dd_add(gs, dd{X[m + 24 + w], X[m + 32 + w]});
-      }
-      if (lb < 0) lb = 0;
-      if (ub == 0x7fffffff) ub = m - 1;
-      if (mi == 0x7fffffff) mi = 0;
-      const double l10_2 = 0.30102999566398119521;
-      const double lbv = a.diffv[lb] / l10_2, mlev = a.diffv[mi] / l10_2, ubv = a.diffv[ub] / l10_2;
-      double ce = 0.0;
-      if (lbv > 0) ce = lbv;
-      if (ubv < 0) ce = ubv;
-      const double gsd = dd_to_d(gs);
-      const double zv = (X[a.zi] + 1e-15) / rs2;
-      double zl = qnorm(gsd, false);
-      if (zl > 0) zl = 0;
-      double zg = qnorm(gsd + zv, false);
-      if (zg < 0) zg = 0;
-      const double z = (fabs(zl) > fabs(zg)) ? zl : zg;
-      const long long N = a.res_ld;
-      a.res[g] = lbv;
-      a.res[g + N] = mlev;
-      a.res[g + 2 * N] = ubv;
-      a.res[g + 3 * N] = ce;
-      a.res[g + 4 * N] = z;
-    }
-    __syncthreads();
-  }
-}
-
-// Test hook (scde_ctx_inject_fault "handoff_spin"): one wave that spins for `cycles` shader clocks,
-// queued on a producing stream before a cross-stream handoff's event -- a consumer that misses its
-// wait then reads the producer's output before it is written, every time, not once in a while.
-__global__ void k_spin(long long cycles) {
-  const long long t0 = clock64();
-  while (clock64() - t0 < cycles) __builtin_amdgcn_s_sleep(1);
-}
-
 // ================================================================== launchers
-static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-hipError_t launch_spin(hipStream_t s, long long cycles) {
-  if (cycles <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, std::min(cycles, 100000000LL));  // (at most ~0.05 s)
-  return hipGetLastError();
-}
-
 hipError_t launch_cell_prep(const double* models, int ncells, int G, int GS, const double* mag, int lt, int sq,
                             double* mu, double* lcfp, double* lcfpr, double* theta, double* cellscal,
                             double* pq, hipStream_t s, double* cfp) {
@@ -4258,7 +2929,6 @@ hipError_t launch_cell_prep(const double* models, int ncells, int G, int GS, con
                      lcfpr, theta, cellscal, lt ? nullptr : pq, cfp);
   return hipGetLastError();
 }
-
 
 hipError_t launch_col_consts(const int* ucl, const long long* ucl_off, long long ncols, int ncells,
                              const double* theta, int GS, const double* cellscal, double* colc, hipStream_t s) {
@@ -4334,44 +3004,6 @@ hipError_t launch_base_cols(const int* ucl, const long long* ucl_off, int ncells
   return hipGetLastError();
 }
 
-// 16-bit host counts widened to the int32 counts the unique-set build reads (U16Ring uploads)
-__global__ __launch_bounds__(256) void k_widen16(const unsigned short* __restrict__ in, int* __restrict__ out,
-                                                 long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[i];
-}
-
-// out[idx] = count for each listed (idx, count): the counts the 16-bit upload could not carry
-__global__ __launch_bounds__(256) void k_patch32(const int2* __restrict__ exc, long long n, int* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[exc[i].x] = exc[i].y;
-}
-
-hipError_t launch_patch32(const int2* exc, size_t n, int* out, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_patch32, dim3((unsigned)div_up((long long)n, 256)), dim3(256), 0, s, exc, (long long)n, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_widen16(const unsigned short* in, int* out, size_t n, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_widen16, dim3((unsigned)div_up((long long)n, 256)), dim3(256), 0, s, in, out, (long long)n);
-  return hipGetLastError();
-}
-
-hipError_t launch_ell(const int* uci, long long ld_uci, int ngenes, int ncells, const long long* ucl_off,
-                      const int* base_col, int stride, int pad_col, int padto, int2* ent, int* nnz, hipStream_t s,
-                      int cell_off, const int* ucl, unsigned* key, int* idx, int kg0, int kgn, int kch, int desc) {
-  if (ngenes <= 0) return hipSuccess;
-  if (padto == 64 ? stride < ((ncells + 63) & ~63) + 8 || stride < 72 : stride < ((ncells + 7) & ~7) + 8)
-    return hipErrorInvalidValue;
-  if (cell_off < 0) return hipErrorInvalidValue;
-  if (key && (!ucl || !idx || kch < 1 || kgn < kg0 + ngenes || kch > kgn)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_ell, dim3(div_up(ngenes, 64)), dim3(64 * kEllWaves), 0, s, uci, ld_uci, ngenes, ncells, ucl_off,
-                     base_col, stride, pad_col, padto, ent, nnz, cell_off, ucl, key, idx, kg0, kgn, kch, desc);
-  return hipGetLastError();
-}
-
 hipError_t launch_delta(const double* T, const long long* ucl_off, int ncells, long long ncols, const int* base_col,
                         int G, int GS, double* D, hipStream_t s) {
   hipLaunchKernelGGL(k_delta, dim3(div_up(ncols + 1, 4)), dim3(256), 0, s, T, ucl_off, ncells, ncols, base_col, G,
@@ -4392,30 +3024,6 @@ hipError_t launch_stretch_zu(const double* U, const int* base_col, int ncells, c
   if (nsets <= 0 || Bp <= 0) return hipSuccess;
   if (gsets < 0 || gsets > nsets || gsplit < 0 || gsplit > ncells) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_stretch_zu, dim3(Bp, nsets), dim3(256), 0, s, U, base_col, ncells, Wt, Bp, ZU, gsets, gsplit);
-  return hipGetLastError();
-}
-
-static inline int block_for_grid(int G, int* kpt) {
-  int b = ((G + 63) / 64) * 64;
-  *kpt = 1;
-  while (b > 1024) {
-    *kpt *= 2;
-    b = ((G + *kpt * 64 - 1) / (*kpt * 64)) * 64;
-  }
-  return b;
-}
-
-hipError_t launch_boot(const BootArgs& a, hipStream_t s) {
-  if (a.ngenes <= 0) return hipSuccess;
-  int kpt;
-  const int block = block_for_grid(a.G, &kpt);
-  const int grid = a.ngenes;
-  switch (kpt) {
-    case 1: hipLaunchKernelGGL(k_boot<1>, dim3(grid), dim3(block), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(k_boot<2>, dim3(grid), dim3(block), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(k_boot<4>, dim3(grid), dim3(block), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
   return hipGetLastError();
 }
 
@@ -4702,118 +3310,9 @@ hipError_t launch_boot_tiles(const Boot2Args& a, const TileBootArgs& tb, hipStre
   return hipGetLastError();
 }
 
-hipError_t launch_boot_exact(const ExactArgs& a, hipStream_t s) {
-  const int g_lo = a.g_hi >= 0 ? a.g_lo : 0, g_hi = a.g_hi >= 0 ? a.g_hi : a.ngenes;
-  if (g_lo < 0 || g_hi > a.ngenes || g_lo > g_hi) return hipErrorInvalidValue;
-  if (g_hi == g_lo) return hipSuccess;
-  ExactArgs b = a;
-  b.g_lo = g_lo;  // blockIdx.x + g_lo
-  int kpt;
-  const int block = block_for_grid(a.G, &kpt);
-  const dim3 grid(g_hi - g_lo);
-  switch (kpt) {
-    case 1: hipLaunchKernelGGL(k_boot_exact<1>, grid, dim3(block), 0, s, b); break;
-    case 2: hipLaunchKernelGGL(k_boot_exact<2>, grid, dim3(block), 0, s, b); break;
-    case 4: hipLaunchKernelGGL(k_boot_exact<4>, grid, dim3(block), 0, s, b); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_noboot(const NoBootArgs& a, hipStream_t s) {
-  if (a.ngenes <= 0) return hipSuccess;
-  int kpt;
-  const int block = block_for_grid(a.G, &kpt);
-  switch (kpt) {
-    case 1: hipLaunchKernelGGL(k_noboot<1>, dim3(a.ngenes), dim3(block), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(k_noboot<2>, dim3(a.ngenes), dim3(block), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(k_noboot<4>, dim3(a.ngenes), dim3(block), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_ensemble_cols(const double* T, long long ncols, int G, int GS, double* E, hipStream_t s) {
   if (ncols <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_ensemble_cols, dim3(div_up(ncols, 4)), dim3(256), 0, s, T, ncols, G, GS, E);
   return hipGetLastError();
 }
-
-hipError_t launch_modes(const int* uci, long long ld_uci, int ngenes, int ncells, const long long* ucl_off,
-                        const int* maxi, const double* mag, double* modes, long long mg, long long mc,
-                        hipStream_t s) {
-  const long long n = (long long)ngenes * ncells;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_modes, dim3(div_up(n, 256)), dim3(256), 0, s, uci, ld_uci, ngenes, ncells, ucl_off, maxi,
-                     mag, modes, mg, mc);
-  return hipGetLastError();
-}
-
-hipError_t launch_post(const int* uci, long long ld_uci, int ngenes, int c, const long long* ucl_off,
-                       const double* T, int G, int GS, double* post, long long pg, long long pk, hipStream_t s) {
-  const long long n = (long long)ngenes * G;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_post, dim3(div_up(n, 256)), dim3(256), 0, s, uci, ld_uci, ngenes, c, ucl_off, T, G, GS,
-                     post, pg, pk);
-  return hipGetLastError();
-}
-
-hipError_t launch_cell_minmax(const int* counts, long long ld, long long g0, int ngenes, int ncells,
-                              const int* cellidx, int* cmax, int* cmin, hipStream_t s) {
-  if (ncells <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_cell_minmax, dim3(ncells), dim3(256), 0, s, counts, ld, g0, ngenes, cellidx, cmax, cmin);
-  return hipGetLastError();
-}
-
-hipError_t launch_mark(const int* counts, long long ld, long long g0, int ngenes, int ncells, const int* cellidx,
-                       const long long* woff, unsigned long long* bits, hipStream_t s, int* flags) {
-  const long long n = (long long)ngenes * ncells;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL((k_mark<8, 16>), dim3(div_up(ngenes, 256 * 8), ncells), dim3(256), 0, s, counts, ld, g0,
-                     ngenes, cellidx, woff, bits, flags);
-  return hipGetLastError();
-}
-
-hipError_t launch_rank(const unsigned long long* bits, const long long* woff, int ncells, int* rank, int* nuniq,
-                       hipStream_t s, const int* flags_in, int* flags_out) {
-  if (ncells <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rank, dim3(ncells), dim3(256), 0, s, bits, woff, rank, nuniq, flags_in, flags_out);
-  return hipGetLastError();
-}
-
-hipError_t launch_fill_ucl(const unsigned long long* bits, const long long* woff, int ncells, const int* rank,
-                           const long long* ucl_off, int* ucl, hipStream_t s) {
-  if (ncells <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_fill_ucl, dim3(ncells), dim3(256), 0, s, bits, woff, rank, ucl_off, ucl);
-  return hipGetLastError();
-}
-
-hipError_t launch_uci(const int* counts, long long ld, long long g0, int ngenes, int ncells, const int* cellidx,
-                      const long long* woff, const unsigned long long* bits, const int* rank, int* uci,
-                      hipStream_t s) {
-  const long long n = (long long)ngenes * ncells;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_uci, dim3(div_up(n, 256)), dim3(256), 0, s, counts, ld, g0, ngenes, ncells, cellidx, woff,
-                     bits, rank, uci);
-  return hipGetLastError();
-}
-
-hipError_t launch_colmajor_to_rows(const double* src, int nrows, int ncols, int GS, double* dst, hipStream_t s) {
-  const long long n = (long long)nrows * ncols;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_colmajor_to_rows, dim3(div_up(n, 256)), dim3(256), 0, s, src, nrows, ncols, GS, dst);
-  return hipGetLastError();
-}
-
-hipError_t launch_ratio_summary(const RatioArgs& a, hipStream_t s) {
-  if (a.ngenes <= 0) return hipSuccess;
-  const int NA = (a.n + 9) & ~1;
-  const size_t shm = sizeof(double) * (size_t)(4 * NA + 2 + ((2 * a.n - 1 + 49) & ~1) + 16) + sizeof(int) * 32;
-  // R = 4: a 4-step unrolled loop rotates the R-wide register window fully (no moves);
-  // measured fastest of R = 4, 5, 8 at n = 401, in blocks of 128 threads
-  const int grid = a.ngenes < 65536 ? a.ngenes : 65536;
-  hipLaunchKernelGGL(k_ratio_summary<4>, dim3(grid), dim3(128), shm, s, a);
-  return hipGetLastError();
-}
-
 }  // namespace scde

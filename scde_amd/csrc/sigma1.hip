@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace scde {
 namespace {
@@ -35,8 +36,7 @@ constexpr int kSB = 256;                           // threads per problem
 constexpr int kST = 32, kSK = 32, kSS = kSK + 2;   // Gram tile, chunk of the summed side, LDS row stride
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -44,26 +44,11 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }
 
 __device__ __forceinline__ double block_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  v = wave_max(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-// Sturm count of the pivots <= 0 of T - x I (d: diagonal, e2: squared off-diagonal)
-__device__ __forceinline__ int sturm_count(const double* __restrict__ d, const double* __restrict__ e2, int n,
-                                           double x, double pivmin) {
-  double q = d[0] - x;
-  if (fabs(q) < pivmin) q = -pivmin;
-  int c = q <= 0.0;
-  for (int i = 1; i < n; ++i) {
-    q = d[i] - e2[i - 1] / q - x;
-    if (fabs(q) < pivmin) q = -pivmin;
-    c += q <= 0.0;
-  }
-  return c;
 }
 
 __global__ __launch_bounds__(kSB) void k_sigma1sq(const double* __restrict__ X, int ncells, long long ngenes,

@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace scde {
 namespace {
@@ -36,21 +37,10 @@ namespace {
 constexpr int kWB = SCDE_WPCA_BLOCK;  // block size (waves = kWB / 64)
 constexpr int kNW = kWB / 64;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-
 // Fixed-order block sum over NW waves; every thread gets the total.  red: NW doubles.
 template <int NW = kNW>
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
-  v = wave_sum_d(v);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -61,7 +51,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
 }
 template <int NW = kNW>
 __device__ __forceinline__ double block_max_d(double v, double* red) {
-  v = wave_max_d(v);
+  v = wave_max(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -366,7 +356,7 @@ __global__ __launch_bounds__(kWB) void k_wpca_em(const double* __restrict__ M, c
         }
       }
 #pragma unroll
-      for (int q = 0; q < NM; ++q) acc[q] = wave_sum_d(acc[q]);
+      for (int q = 0; q < NM; ++q) acc[q] = wave_sum(acc[q]);
       if (lane == 0)
 #pragma unroll
         for (int q = 0; q < NM; ++q) mom[(long long)g * NM + q] = acc[q];
@@ -541,41 +531,18 @@ constexpr int kMsNT = 1024, kMsNW = 16, kMsSG = 5, kMsGCH = 16;
 #define SCDE_WPCA_PREFETCH 1  // k_wpca_ms1: the next gene's M / W loads issued ahead of the current gene's arithmetic
 #endif
 
-__device__ __forceinline__ void swap32d(double& a, double& b) {
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false,
-                                                   false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false,
-                                                   false);
-  a = __hiloint2double((int)hi[0], (int)lo[0]);
-  b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ void swap16d(double& a, double& b) {
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false,
-                                                   false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false,
-                                                   false);
-  a = __hiloint2double((int)hi[0], (int)lo[0]);
-  b = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-template <int CTRL>
-__device__ __forceinline__ double dppd(double x) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
 // Sum reduce-scatter of 16 values over the wave: lane l ends with the wave total of
 // value (l >> 2) & 15.  Stages pair lanes by bit 5, 4 (permlane swaps), 3 (row mirror,
 // lane ^ 15), 2 (half mirror, lane ^ 7), then 1, 0 (quad perms).
 __device__ __forceinline__ double rs16_sum(double (&v)[16], int lane) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    swap32d(v[j], v[j + 8]);
+    swap32(v[j], v[j + 8]);
     v[j] = v[j] + v[j + 8];
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    swap16d(v[j], v[j + 4]);
+    swap16(v[j], v[j + 4]);
     v[j] = v[j] + v[j + 4];
   }
   {
@@ -583,24 +550,24 @@ __device__ __forceinline__ double rs16_sum(double (&v)[16], int lane) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const double lo = v[j], hi = v[j + 2];
-      v[j] = (up ? hi : lo) + dppd<0x140>(up ? lo : hi);
+      v[j] = (up ? hi : lo) + dpp_d<kDppMirror>(up ? lo : hi);
     }
   }
   {
     const bool up = (lane & 4) != 0;
     const double lo = v[0], hi = v[1];
-    v[0] = (up ? hi : lo) + dppd<0x141>(up ? lo : hi);
+    v[0] = (up ? hi : lo) + dpp_d<kDppHalfMirror>(up ? lo : hi);
   }
   double x = v[0];
-  x = x + dppd<0x4E>(x);
-  x = x + dppd<0xB1>(x);
+  x = x + dpp_d<kDppXor2>(x);
+  x = x + dpp_d<kDppXor1>(x);
   return x;
 }
 
 template <int NW, int V>
 __device__ __forceinline__ void block_sum_vec(double (&v)[V], double* red) {
 #pragma unroll
-  for (int i = 0; i < V; ++i) v[i] = wave_sum_d(v[i]);
+  for (int i = 0; i < V; ++i) v[i] = wave_sum(v[i]);
   __syncthreads();
   if ((threadIdx.x & 63) == 0)
 #pragma unroll

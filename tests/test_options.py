@@ -32,6 +32,7 @@ def test_removed_options_are_gone():
                "lane_prio", "lane_thread", "interleave", "defer_boot", "upload_staged", "upload_threads", "pair_cells",
                "gene_blocks", "gene_direct", "rest_thread", "tables_pair", "task_cols", "ratio_window", "ratio_block"}
     assert not (removed & _implemented())
-    kern = open(os.path.join(ROOT, "scde_amd", "csrc", "kernels.hip")).read()
+    kern = "".join(open(os.path.join(ROOT, "scde_amd", "csrc", f)).read()
+                   for f in ("kernels.hip", "unique.hip", "boot.hip", "ratio.hip"))
     for k in ("k_boot2t", "k_tables_reg", "tables_cols_lean"):
         assert k + "<" not in kern and k + "(" not in kern, k
