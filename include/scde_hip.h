@@ -872,7 +872,7 @@ int scde_top_aspects(scde_ctx* ctx, const double* x, const double* w, const doub
 
 /* ---------------------------------------------------------------- knn.error.models, neighbourhood stage
  * What knn.error.models computes before its mixture fit (R/functions.R:1180-1226; csrc/knn.hip,
- * driven by scde_amd/knn.py; the fit itself is not part of the library).  counts is int32,
+ * driven by scde_amd/knn.py; the fit itself follows below, scde_knn_fit_*).  counts is int32,
  * ngenes x ncells column-major with leading dimension ld; thr is min.count.threshold and an entry
  * is valid when counts[g, j] >= thr.  Counts are not negative (not checked here: a negative
  * valid count, possible with thr <= 0, gives sqrt's NaN in the similarity and a negative value
@@ -914,6 +914,49 @@ int scde_knn_magnitudes_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, in
                             int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove);
 int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const int* nb,
                              int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove);
+
+/* ---------------------------------------------------------------- knn.error.models, mixture fit
+ * One two-component EM per cell (fit.nb2gth.mixture.model and get.compressed.v1.model,
+ * R/functions.R:3653-3660, 4058-4187, 3422-3434; csrc/knn_fit.hip; the contract, step by step, is
+ * DESIGN.md section 4.15).  fpm and fail_prior are host ngenes x ncells column-major, as
+ * scde_amd/knn.py's knn_model_inputs gives them: a gene is valid in a cell where fail_prior is not
+ * NaN, and fail_prior is then the starting posterior of the failed component.  Per cell, with
+ * y = the valid genes' counts, x = their fpm, l = log x, and posteriors (p1, p2 = 1 - p1), up to
+ * max_iter rounds of
+ *   concomitant  beta maximising sum p2 log s(eta) + (1 - p2) log(1 - s(eta)), eta = b0 + b1 l + b2 l^2,
+ *                s the logistic function: Newton from 0, a step halved while it lowers the objective;
+ *                no convergence within 50 steps (separable data) fails the cell
+ *   slope        a = sum p2 y / sum p2 x, mu = a x
+ *   theta        the root in [theta_lo, theta_hi] of MASS::theta.md's moment equation with weights
+ *                p2, or the bound on the side the sign indicates
+ *   curve        (local_theta) b, t, m, s, r minimising sum p2 alpha^alpha_weight_power
+ *                (log alpha - f(l))^2, f(l) = b + (t - b) / (1 + 10^((m - l) s))^r,
+ *                alpha = (y / mu - 1)^2 - 1 / mu clamped to [1 / theta_hi, 1 / theta_lo], in R's box,
+ *                by the project's projected Levenberg-Marquardt from R's start
+ *   E-step       log p1 ~ log(1 - s(eta)) + dpois(y, 0.1), log p2 ~ log s(eta) + dnbinom(y, size =
+ *                theta or exp(-f(l)) clamped to the range, mu); llh = sum of the log-sum-exps
+ * until |llh - llh_old| / (|llh| + 0.1) < 1e-6.  Row c of models (host, ncells x 12 column-major,
+ * the columns conc.b, conc.a, fail.r, corr.b, corr.a, corr.theta, corr.ltheta.{b,t,m,s,r}, conc.a2)
+ * holds b0, b1, log 0.1, log a, 1, theta, the curve (NaN without local_theta), b2 of the last
+ * M-step.  iterations[c] is the number of rounds, llh[c] the last log-likelihood, status[c] 0, or
+ * 1 (fewer than 3 valid genes), 2 (sum p2 x = 0), 3 (a parameter or the likelihood is not
+ * finite): the row and llh are then NaN.  clusters (int32, 1 / 2, 0 outside the valid genes and
+ * in a failed cell) and post (the failed component's posterior, NaN likewise) are host ngenes x
+ * ncells column-major from the last E-step, or NULL.  lds_genes: a cell with at most this many
+ * valid genes keeps its per-gene vectors in LDS, a larger one in an HBM workspace (0: the default,
+ * 2048; at most 3376; the results are the same bits either way).  One launch, one workgroup per
+ * cell; every sum is taken in an order fixed by the cell's valid-gene count alone and there are
+ * no floating-point atomics: results are bit-repeatable, the same whichever cells share the call,
+ * and the two entries agree bit for bit.  0 < theta_lo < theta_hi, max_iter >= 1, at most 8192
+ * cells.  ctx may be NULL. */
+int scde_knn_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const double* fpm,
+                     const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
+                     double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
+                     double* llh, int* status, int* clusters, double* post);
+int scde_knn_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* fpm,
+                      const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
+                      double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
+                      double* llh, int* status, int* clusters, double* post);
 
 /* Free and total bytes of the context's device (hipMemGetInfo). */
 int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);

@@ -17,8 +17,8 @@ from .cluster import (HClust, cutree, hclust, hclust_batch, leaf_order_length, o
 from .distance import (direct_dropout_distance, mode_relative_distance, reciprocal_distance,  # noqa: F401
                        weighted_correlation)
 from .embedding import TsneState, tsne_affinities, tsne_embedding, tsne_iterate  # noqa: F401
-from .knn import (estimate_library_sizes, knn_cell_data, knn_cell_similarity, knn_expected_magnitudes,  # noqa: F401
-                  knn_model_inputs, knn_neighbours, tmm_norm_factors)
+from .knn import (estimate_library_sizes, knn_cell_data, knn_cell_similarity, knn_error_models,  # noqa: F401
+                  knn_expected_magnitudes, knn_fit_models, knn_model_inputs, knn_neighbours, tmm_norm_factors)
 from .prior import expression_prior  # noqa: F401
 from .top_aspects import pagoda_effective_cells, pagoda_top_aspects, top_aspects_table  # noqa: F401
 from .varnorm import (EdfTable, fit_trend, load_edf_table, pagoda_subtract_aspect, pagoda_varnorm)  # noqa: F401

@@ -41,7 +41,7 @@ EXPORTS = [
     "scde_tsne_ws_bytes", "scde_tsne_affinities_dev", "scde_tsne_iterate_dev", "scde_tsne_cost_dev", "scde_tsne_host",
     "scde_top_aspects", "scde_top_aspects_dev",
     "scde_knn_similarity_dev", "scde_knn_similarity_host", "scde_knn_neighbours",
-    "scde_knn_magnitudes_dev", "scde_knn_magnitudes_host",
+    "scde_knn_magnitudes_dev", "scde_knn_magnitudes_host", "scde_knn_fit_dev", "scde_knn_fit_host",
 ]
 
 
@@ -176,6 +176,9 @@ def lib():
     L.scde_knn_similarity_dev.argtypes = L.scde_knn_similarity_host.argtypes = [P, P, i64, i, i, i, P]
     L.scde_knn_neighbours.argtypes = [P, P, i, P, i, i, P]
     L.scde_knn_magnitudes_dev.argtypes = L.scde_knn_magnitudes_host.argtypes = [P, P, i64, i, i, P, i, P, i, d, P, P]
+    if hasattr(L, "scde_knn_fit_dev"):  # (an SCDE_LIB build from before the mixture fit, in an A/B run, lacks it)
+        L.scde_knn_fit_dev.argtypes = L.scde_knn_fit_host.argtypes = [P, P, i64, i, i, P, P, i, d, d, d, i, i, P, P, P,
+                                                                      P, P, P]
     _lib = L
     return L
 

@@ -673,4 +673,90 @@ int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int n
   RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
   return scde_knn_magnitudes_dev(ctx, dev, ngenes, ngenes, ncells, nb, kmax, ls, thr, trim, fpm, nabove);
 }
+
+// ------------------------------------------------------------------ knn.error.models' mixture fit
+// knn_fit.hip; contract in scde_hip.h.
+static int knn_fit_check(const double* fpm, const double* fail_prior, double theta_lo, double theta_hi, double awp,
+                         int max_iter, int lds_genes, const void* models, const void* iterations, const void* llh,
+                         const void* status) {
+  if (!fpm || !fail_prior || !models || !iterations || !llh || !status)
+    return fail(SCDE_EARG, "knn_fit: null argument");
+  if (!(theta_lo > 0.0) || !(theta_hi > theta_lo) || std::isinf(theta_hi))
+    return fail(SCDE_EARG, "knn_fit: the theta range must be 0 < lo < hi < Inf");
+  if (!std::isfinite(awp)) return fail(SCDE_EARG, "knn_fit: alpha_weight_power must be finite");
+  if (max_iter < 1) return fail(SCDE_EARG, "knn_fit: max_iter must be at least 1");
+  if (lds_genes < 0 || lds_genes > knn_fit_lds_genes_max())
+    return fail(SCDE_EARG, "knn_fit: lds_genes must lie in [0, %d]", knn_fit_lds_genes_max());
+  return SCDE_OK;
+}
+
+int scde_knn_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const double* fpm,
+                     const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
+                     double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
+                     double* llh, int* status, int* clusters, double* post) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "knn_fit"));
+  RCHK(knn_fit_check(fpm, fail_prior, theta_lo, theta_hi, alpha_weight_power, max_iter, lds_genes, models, iterations,
+                     llh, status));
+  const int N = ngenes, C = ncells;
+  const int cap = lds_genes > 0 ? lds_genes : 2048;
+  long long nmax = 0;  // the largest cell's valid genes
+  for (int c = 0; c < C; ++c) {
+    long long n = 0;
+    const double* f = fail_prior + (size_t)c * N;
+    for (int g = 0; g < N; ++g) n += std::isnan(f[g]) ? 0 : 1;
+    nmax = std::max(nmax, n);
+  }
+  RCHK(use_ctx(ctx));
+  int grid = 1;
+  HCHK(knn_fit_resident_groups(cap, &grid));
+  grid = std::min(grid, C);
+  const size_t nc = std::max<size_t>(1, (size_t)N * C);
+  const size_t wsb = nmax > cap ? knn_fit_ws_bytes(nmax) * (size_t)grid : 0;
+  if (ctx->kf_fpm.ensure(sizeof(double) * nc) != hipSuccess || ctx->kf_fp.ensure(sizeof(double) * nc) != hipSuccess ||
+      (wsb && ctx->kf_ws.ensure(wsb) != hipSuccess) ||
+      (clusters && ctx->kf_cl.ensure(sizeof(int) * nc) != hipSuccess) ||
+      (post && ctx->kf_post.ensure(sizeof(double) * nc) != hipSuccess))
+    return fail_oom("knn_fit: out of memory: %d x %d inputs and a workspace of %zu bytes", N, C, wsb);
+  HCHK(ctx->kf_models.ensure(sizeof(double) * 12 * (size_t)C));
+  HCHK(ctx->kf_llh.ensure(sizeof(double) * (size_t)C));
+  HCHK(ctx->kf_int.ensure(sizeof(int) * 2 * (size_t)C));
+  if (N > 0) {
+    HCHK(hipMemcpyAsync(ctx->kf_fpm.p, fpm, sizeof(double) * (size_t)N * C, hipMemcpyHostToDevice, ctx->stream));
+    HCHK(hipMemcpyAsync(ctx->kf_fp.p, fail_prior, sizeof(double) * (size_t)N * C, hipMemcpyHostToDevice,
+                        ctx->stream));
+  }
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_knn_fit(counts_dev, ld, N, C, ctx->kf_fpm.as<double>(), ctx->kf_fp.as<double>(), local_theta != 0,
+                      theta_lo, theta_hi, alpha_weight_power, max_iter, cap, wsb ? ctx->kf_ws.as<char>() : nullptr,
+                      nmax, grid, ctx->kf_models.as<double>(), ctx->kf_int.as<int>(), ctx->kf_llh.as<double>(),
+                      ctx->kf_int.as<int>() + C, clusters ? ctx->kf_cl.as<int>() : nullptr,
+                      post ? ctx->kf_post.as<double>() : nullptr, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(models, ctx->kf_models.p, sizeof(double) * 12 * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(iterations, ctx->kf_int.p, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
+  HCHK(hipMemcpyAsync(status, ctx->kf_int.as<int>() + C, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost,
+                      ctx->stream));
+  HCHK(hipMemcpyAsync(llh, ctx->kf_llh.p, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
+  if (clusters && N > 0)
+    HCHK(hipMemcpyAsync(clusters, ctx->kf_cl.p, sizeof(int) * (size_t)N * C, hipMemcpyDeviceToHost, ctx->stream));
+  if (post && N > 0)
+    HCHK(hipMemcpyAsync(post, ctx->kf_post.p, sizeof(double) * (size_t)N * C, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  return SCDE_OK;
+}
+
+int scde_knn_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* fpm,
+                      const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
+                      double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
+                      double* llh, int* status, int* clusters, double* post) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "knn_fit"));
+  RCHK(knn_fit_check(fpm, fail_prior, theta_lo, theta_hi, alpha_weight_power, max_iter, lds_genes, models, iterations,
+                     llh, status));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_knn_fit_dev(ctx, dev, ngenes, ngenes, ncells, fpm, fail_prior, local_theta, theta_lo, theta_hi,
+                          alpha_weight_power, max_iter, lds_genes, models, iterations, llh, status, clusters, post);
+}
 }  // extern "C"

@@ -255,6 +255,9 @@ struct scde_ctx {
   // before they go to the host
   Buf kn_sim, kn_nb, kn_int, kn_ls, kn_fpm, kn_nab;
   int kn_sim_c = -1, kn_nb_c = -1, kn_nb_k = -1;
+  // knn.error.models' mixture fit: fpm and the starting posteriors staged, the workspace of the
+  // cells too large for LDS, the results before they go to the host
+  Buf kf_fpm, kf_fp, kf_ws, kf_models, kf_int, kf_llh, kf_cl, kf_post;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters

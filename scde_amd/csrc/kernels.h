@@ -572,6 +572,21 @@ hipError_t launch_knn_neighbours(const double* sim, int C, const int* groups, co
 hipError_t launch_knn_magnitudes(const int* counts, long long ld, int N, int C, const int* nb, int kmax,
                                  const double* ls, int thr, double trim, double* fpm, int* nabove, hipStream_t s);
 
+// ---- knn.error.models' mixture fit (knn_fit.hip; contract in include/scde_hip.h).  fpm, fp (the
+// starting failed-component posteriors, NaN outside a cell's valid genes), clusters and post are
+// N x C dense; models is C x 12 column-major.  A cell with at most lds_genes valid genes keeps its
+// per-gene vectors in LDS, a larger one in its workgroup's slice of ws (knn_fit_ws_bytes(ws_cap)
+// bytes per workgroup, ws_cap at least the largest cell's valid genes; ws may be null when no
+// cell exceeds lds_genes).  grid: workgroups launched (at most C are).
+int knn_fit_lds_genes_max();
+size_t knn_fit_lds_bytes(int lds_genes);
+size_t knn_fit_ws_bytes(long long ws_cap);
+hipError_t knn_fit_resident_groups(int lds_genes, int* groups);
+hipError_t launch_knn_fit(const int* counts, long long ld, int N, int C, const double* fpm, const double* fp,
+                          int local_theta, double theta_lo, double theta_hi, double awp, int max_iter, int lds_genes,
+                          char* ws, long long ws_cap, int grid, double* models, int* iters, double* llh, int* status,
+                          int* clusters, double* post, hipStream_t s);
+
 // ---- pagoda.top.aspects' matrix step (top_aspects.hip; contract in include/scde_hip.h).  x, w,
 // xv, xvw: m x C row-major (an aspect contiguous); num: m values.  Row r of xv is x's row centred
 // times num[r] / sqrt(its variance, denominator C - 1), row r of xvw is w's row over its sum

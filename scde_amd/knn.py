@@ -1,5 +1,6 @@
-"""The neighbourhood stage of ``knn.error.models`` (R/functions.R:1158-1237), on the GPU
-(csrc/knn.hip): everything PAGODA's error-model fitter computes before its per-cell mixture fit.
+"""``knn.error.models`` (R/functions.R:1158-1299) on the GPU: the neighbourhood stage
+(csrc/knn.hip), everything PAGODA's error-model fitter computes before its per-cell mixture fit,
+and the fit itself (csrc/knn_fit.hip).
 
   * ``estimate_library_sizes``    estimate.library.sizes with ``vil = counts >= thr`` (host)
   * ``tmm_norm_factors``          edgeR's calcNormFactors(method = "TMM"), restated (host)
@@ -8,9 +9,12 @@
   * ``knn_expected_magnitudes``   trimmed mean of the neighbours' library-scaled counts (fpm)
   * ``knn_model_inputs``          the chain, with the counts resident throughout
   * ``knn_cell_data``             one cell's ``data.frame(count, fpm)`` and ``cp``
+  * ``knn_fit_models``            fit.nb2gth.mixture.model + get.compressed.v1.model of every cell
+  * ``knn_error_models``          the whole function: R's joint model matrix ``jmm``
 
-The mixture fit itself (fit.nb2gth.mixture.model and what follows it) is not built: the results
-here are exactly its inputs.  ``counts`` is an integer genes x cells matrix or a resident
+The fit is the project's statement of flexmix's EM, compared with R's
+stored result on the pollen data (tests/test_gpu_knn_fit.py); ``linear_fit=False``
+(fit.nb2.mixture.model) is not built.  ``counts`` is an integer genes x cells matrix or a resident
 ``DeviceCounts``; ``thr`` is min.count.threshold and an entry is valid when ``counts >= thr``.
 The TMM factors are written from Robinson & Oshlack (2010) with edgeR's documented defaults and
 were not checked against edgeR; ``norm_factors=`` / ``library_sizes=`` take a caller's values.
@@ -354,6 +358,95 @@ def _fetch_counts(dc):
     if out.nbytes:
         check(lib().scde_d2h(dc.ctx.handle, api._p(out), dc.ptr, out.nbytes))
     return out
+
+
+# ================================================================== the mixture fit
+FIT_STATUS = {0: "ok", 1: "fewer than 3 valid genes", 2: "no weight on the correlated component",
+              3: "a parameter or the likelihood is not finite"}
+
+
+def knn_fit_models(inputs, counts, local_theta_fit=None, theta_fit_range=(1e-2, 1e2), alpha_weight_power=0.5,
+                   iter=50, linear_fit=True, return_details=False, lds_genes=0, ctx: api.Context | None = None):
+    """The per-cell EM mixture fit (fit.nb2gth.mixture.model + get.compressed.v1.model; contract in
+    include/scde_hip.h and DESIGN.md section 4.15) on what ``knn_model_inputs`` returned.
+
+    Returns the cells x 12 model matrix in ``models.MODEL_COLUMNS``' order (a failed cell's row is
+    NaN; without local theta the ``corr.ltheta.*`` columns are NaN), and with ``return_details`` a
+    dict as well: ``iterations``, ``llh``, ``status`` (per cell; ``FIT_STATUS``), ``clusters``
+    (genes x cells int32: 1 / 2, R's ``clusters(m1)``, 0 outside the valid genes) and
+    ``posteriors`` (genes x cells: the failed component's final posterior, NaN outside).
+    ``local_theta_fit`` defaults to True, as in R; ``iter = 1`` is one M-step and one E-step from the
+    starting posteriors.  ``lds_genes`` is the C entry's (0: its default)."""
+    if not linear_fit:
+        raise NotImplementedError("linear_fit = False (fit.nb2.mixture.model) is not built")
+    local = True if local_theta_fit is None else bool(local_theta_fit)
+    lo, hi = (float(v) for v in theta_fit_range)
+    dc, mat, N, C = _counts_arg(counts)
+    fpm = np.asfortranarray(inputs["fpm"], dtype=np.float64)
+    fp = np.asfortranarray(inputs["fail_prior"], dtype=np.float64)
+    if fpm.shape != (N, C) or fp.shape != (N, C):
+        raise ValueError("inputs do not belong to these counts")
+    models = np.zeros((C, 12), order="F")
+    its = np.zeros(C, np.int32)
+    status = np.zeros(C, np.int32)
+    llh = np.zeros(C)
+    cl = np.zeros((N, C), np.int32, order="F") if return_details else None
+    post = np.zeros((N, C), order="F") if return_details else None
+    h = _handle(dc, ctx)
+    args = (N, N, C, api._p(fpm), api._p(fp), int(local), lo, hi, float(alpha_weight_power), int(iter),
+            int(lds_genes), api._p(models), api._p(its), api._p(llh), api._p(status), api._p(cl), api._p(post))
+    if dc is not None:
+        check(lib().scde_knn_fit_dev(h, dc.ptr, *args))
+    else:
+        check(lib().scde_knn_fit_host(h, api._p(mat), *args))
+    if not return_details:
+        return models
+    return models, {"iterations": its, "llh": llh, "status": status, "clusters": cl, "posteriors": post}
+
+
+def knn_error_models(counts, groups=None, k=None, min_nonfailed=5, min_count_threshold=1, min_size_entries=2000,
+                     min_fpm=0, cor_method="pearson", fpm_estimate_trim=0.25, linear_fit=True, local_theta_fit=None,
+                     theta_fit_range=(1e-2, 1e2), alpha_weight_power=0.5, iter=50, return_details=False,
+                     ctx: api.Context | None = None):
+    """``knn.error.models`` (R/functions.R:1158-1299): the neighbourhood stage, then every cell's
+    mixture fit, both on the GPU.  Returns R's ``jmm``: a DataFrame of the cells' models, columns in
+    ``models.MODEL_COLUMNS``' order (without the ``corr.ltheta.*`` columns when
+    ``local_theta_fit=False``), rows named by the cells (the counts' column names, or their
+    positions) and ordered by group as R's ``rbind`` over the groups, ``.attrs["groups"]`` the rows'
+    groups.  A cell whose fit fails is dropped with a warning, as R drops a ``try-error``.  With
+    ``return_details``: ``(jmm, details)``, the details of ``knn_fit_models`` (all cells, in the
+    counts' order) and the model inputs under ``"inputs"``."""
+    import pandas as pd
+
+    from .models import MODEL_COLUMNS
+    if not linear_fit:
+        raise NotImplementedError("linear_fit = False (fit.nb2.mixture.model) is not built")
+    local = True if local_theta_fit is None else bool(local_theta_fit)
+    cells = None if isinstance(counts, api.DeviceCounts) else api._counts_matrix(counts)[2]
+    inputs = knn_model_inputs(counts, groups=groups, k=k, min_nonfailed=min_nonfailed,
+                              min_count_threshold=min_count_threshold, min_size_entries=min_size_entries,
+                              min_fpm=min_fpm, fpm_estimate_trim=fpm_estimate_trim, cor_method=cor_method, ctx=ctx)
+    dc = counts if isinstance(counts, api.DeviceCounts) else None
+    host = counts if dc is not None else _host_counts(counts)
+    mm, det = knn_fit_models(inputs, host, local_theta_fit=local, theta_fit_range=theta_fit_range,
+                             alpha_weight_power=alpha_weight_power, iter=iter, return_details=True,
+                             ctx=None if dc is not None else ctx)
+    C = mm.shape[0]
+    names = cells if cells is not None else [str(i) for i in range(C)]
+    for i in np.flatnonzero(det["status"] != 0):
+        warnings.warn(f"ERROR encountered in building a model for cell {names[i]} - skipping the cell. Error: "
+                      f"{FIT_STATUS.get(int(det['status'][i]), 'status %d' % det['status'][i])}")
+    codes = _group_codes(groups, C)
+    order = np.arange(C) if codes is None else np.argsort(codes, kind="stable")
+    order = order[det["status"][order] == 0]
+    cols = [c for c in MODEL_COLUMNS if local or not c.startswith("corr.ltheta.")]
+    jmm = pd.DataFrame({c: mm[order, MODEL_COLUMNS.index(c)] for c in cols}, index=[names[i] for i in order])
+    glab = np.asarray(groups)[order] if groups is not None else np.array(["all"] * len(order))
+    jmm.attrs["groups"] = [str(g) for g in glab]
+    if not return_details:
+        return jmm
+    det["inputs"] = inputs
+    return jmm, det
 
 
 def knn_cell_data(inputs, counts, i):
