@@ -920,9 +920,10 @@ int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int n
  * R/functions.R:3653-3660, 4058-4187, 3422-3434; csrc/knn_fit.hip; the contract, step by step, is
  * DESIGN.md section 4.15).  fpm and fail_prior are host ngenes x ncells column-major, as
  * scde_amd/knn.py's knn_model_inputs gives them: a gene is valid in a cell where fail_prior is not
- * NaN, and fail_prior is then the starting posterior of the failed component.  Per cell, with
- * y = the valid genes' counts, x = their fpm, l = log x, and posteriors (p1, p2 = 1 - p1), up to
- * max_iter rounds of
+ * NaN, and fail_prior is then the starting posterior of the failed component (both NULL: what the
+ * last scde_crossfit_inputs_* call on this context left resident, of the same ngenes and ncells).
+ * Per cell, with y = the valid genes' counts, x = their fpm, l = log x, and posteriors
+ * (p1, p2 = 1 - p1), up to max_iter rounds of
  *   concomitant  beta maximising sum p2 log s(eta) + (1 - p2) log(1 - s(eta)), eta = b0 + b1 l + b2 l^2,
  *                s the logistic function: Newton from 0, a step halved while it lowers the objective;
  *                no convergence within 50 steps (separable data) fails the cell
@@ -957,6 +958,83 @@ int scde_knn_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, 
                       const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
                       double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
                       double* llh, int* status, int* clusters, double* post);
+
+/* ---------------------------------------------------------------- scde.error.models, input stage
+ * What scde.error.models computes before its mixture fit when threshold.segmentation = TRUE
+ * (calculate.crossfit.models' threshold rule and the head of calculate.individual.models,
+ * R/functions.R:3030-3039, 3253-3303; csrc/error_models.hip, driven by scde_amd/error_models.py;
+ * DESIGN.md section 4.16).  counts as above; thr = min.count.threshold >= 1.  groups holds ncells
+ * codes (host; NULL: one group); every group has at least two cells.  Cell i's cross-fit partners
+ * are part[part_off[i] .. part_off[i + 1]) (host, 0-based cells of i's group, not i, none twice;
+ * the pair list seen from both of its cells).  A cell is "paired" when it has a partner.  ls holds
+ * ncells positive finite library sizes.  For gene g and cell i of a group of n cells:
+ *   nabove[g, i]      the number of paired cells j != i of the group with counts[g, j] >= thr
+ *   valid             nabove[g, i] >= min(n - 1, min_nonfailed)
+ *   fpm[g, i]         (sum over the group's cells before i, in cell order, of counts[g, j] / ls[j]
+ *                     + the sum over the cells after i, taken from the last one down) / (n - 1):
+ *                     positive terms only, never a total minus the cell's own term; NaN when not valid
+ *   fail_prior[g, i]  over the partners j with counts[g, i] + counts[g, j] > 0: h of them have
+ *                     counts[g, i] < thr <= counts[g, j], k have not;
+ *                     exp((h log(t) + k log(1 - t)) / (h + k)) with t = 1 - 1e-6 and 1 - t as the
+ *                     doubles they are (R's threshold.prior), 1 - 1e-10 when h + k = 0; NaN when
+ *                     not valid
+ * fpm, fail_prior (double) and nabove (int32) are host ngenes x ncells column-major; each may be
+ * NULL and is then not copied back.  fpm and fail_prior also stay resident in the context: a
+ * following scde_knn_fit_* or scde_nb2_fit_* call on it with the same dimensions may pass NULL for
+ * both.  No floating-point atomics and no order left to chance: results are bit-repeatable and
+ * the two entries agree bit for bit.  At most 8192 cells.  ctx may be NULL. */
+int scde_crossfit_inputs_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const int* groups, const double* ls, const int* part_off, const int* part, int thr,
+                             int min_nonfailed, double* fpm, double* fail_prior, int* nabove);
+int scde_crossfit_inputs_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const int* groups, const double* ls, const int* part_off, const int* part, int thr,
+                              int min_nonfailed, double* fpm, double* fail_prior, int* nabove);
+
+/* ---------------------------------------------------------------- scde.error.models, mixture fit (linear.fit = FALSE)
+ * One two-component EM per cell (fit.nb2.mixture.model: FLXMRnb2glm's fit, glm.nb.fit,
+ * custom.glm.fit and MASS::theta.ml, R/functions.R:3630-3651, 4002-4010, 4434-4547, 4549-4820;
+ * csrc/nb2_fit.hip; the contract, step by step, is DESIGN.md section 4.16).  fpm and fail_prior as
+ * scde_knn_fit_* takes them, or both NULL for what the last scde_crossfit_inputs_* call on this
+ * context left resident (the same ngenes and ncells).  Per cell, with y = the valid genes' counts,
+ * l = log fpm and posteriors (p1 = fail_prior, p2 = 1 - p1), up to max_iter rounds of
+ *   concomitant  (b0, b1) maximising sum p2 log s(eta) + (1 - p2) log(1 - s(eta)), eta = b0 + b1 l:
+ *                scde_knn_fit_*'s Newton on two parameters
+ *   NB component w = p2, divided by 1e6 where y <= 1; genes of weight 0 take no part.  glm.nb.fit with
+ *                the design [1, l] and the log link (mu = max(exp(eta), 2^-52)):
+ *                  IRLS      from a per-gene eta: W = w mu^2 / V(mu), z = eta + (y - mu) / mu, the 2 x 2
+ *                            weighted normal equations by Cholesky; the step halved (at most maxit times)
+ *                            while the deviance is not finite or, from the second iteration on, rises by
+ *                            more than 3e-8 (0.1 + |dev|); until |dev - devold| / (0.1 + |dev|) < 1e-8,
+ *                            at most maxit iterations
+ *                  first     Poisson IRLS from eta = log(y + 0.1), maxit 20
+ *                  theta.ml  t = sum w / sum w (y / mu - 1)^2, then at most 19 Newton steps t = |t|,
+ *                            t += score / info (digamma, trigamma) until |step| <= 2^-13; |t|,
+ *                            clamped to [0.5, Inf)
+ *                  rounds    at most 20, while |Lm0 - Lm| / d1 + |theta0 - theta| > 1e-8 (d1 =
+ *                            sqrt(2 max(1, genes of positive weight - 2)), Lm the NB log-likelihood,
+ *                            Lm0 = Lm + 2 d1 at first): theta.ml at the current mu, then the
+ *                            negative.binomial(theta0) IRLS from the current eta, maxit 200
+ *                a slope c1 < 0 is replaced by (c0, c1) = (mean(y w) / sum w, 0): R's rule, the
+ *                intercept is then a mean where a log mean belongs
+ *   E-step       log p1 ~ log(1 - s(eta)) + dpois(y, background_rate), log p2 ~ log s(eta) +
+ *                dnbinom(y, size = theta, mu = max(exp(c0 + c1 l), 2^-52)); llh = sum of the log-sum-exps
+ * until |llh - llh_old| / (|llh| + 0.1) < 1e-6.  If theta then is exactly 0.5 ("underfit"), glm.nb.fit
+ * runs once more with weight 1 on the genes with p2 > p1 and 0 elsewhere, its first IRLS
+ * negative.binomial(0.5) from eta = log(y + (y == 0) / 6), theta clamped to [0, 1e5], and replaces
+ * (c0, c1, theta).  Row c of models (ncells x 12 column-major, columns as scde_knn_fit_*) holds b0,
+ * b1, log background_rate, c0, c1, theta and six NaN.  iterations, llh, status, clusters, post and
+ * lds_genes as scde_knn_fit_*; status may also be 2 (no gene of positive weight) and 5 (an IRLS
+ * system is singular or not finite, or a halving ran out).  The same guarantees: one launch, one
+ * workgroup per cell, every sum in an order fixed by the cell's valid-gene count and its genes of
+ * weight 0, no floating-point atomics; results are bit-repeatable, the same whichever cells share
+ * the call, and the two entries agree bit for bit.  background_rate > 0, max_iter >= 1, at most
+ * 8192 cells.  ctx may be NULL. */
+int scde_nb2_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const double* fpm,
+                     const double* fail_prior, double background_rate, int max_iter, int lds_genes, double* models,
+                     int* iterations, double* llh, int* status, int* clusters, double* post);
+int scde_nb2_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* fpm,
+                      const double* fail_prior, double background_rate, int max_iter, int lds_genes, double* models,
+                      int* iterations, double* llh, int* status, int* clusters, double* post);
 
 /* Free and total bytes of the context's device (hipMemGetInfo). */
 int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);

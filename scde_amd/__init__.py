@@ -17,6 +17,7 @@ from .cluster import (HClust, cutree, hclust, hclust_batch, leaf_order_length, o
 from .distance import (direct_dropout_distance, mode_relative_distance, reciprocal_distance,  # noqa: F401
                        weighted_correlation)
 from .embedding import TsneState, tsne_affinities, tsne_embedding, tsne_iterate  # noqa: F401
+from .error_models import crossfit_pairs, error_model_inputs, nb2_fit_models, scde_error_models  # noqa: F401
 from .knn import (estimate_library_sizes, knn_cell_data, knn_cell_similarity, knn_error_models,  # noqa: F401
                   knn_expected_magnitudes, knn_fit_models, knn_model_inputs, knn_neighbours, tmm_norm_factors)
 from .prior import expression_prior  # noqa: F401

@@ -42,6 +42,7 @@ EXPORTS = [
     "scde_top_aspects", "scde_top_aspects_dev",
     "scde_knn_similarity_dev", "scde_knn_similarity_host", "scde_knn_neighbours",
     "scde_knn_magnitudes_dev", "scde_knn_magnitudes_host", "scde_knn_fit_dev", "scde_knn_fit_host",
+    "scde_crossfit_inputs_dev", "scde_crossfit_inputs_host", "scde_nb2_fit_dev", "scde_nb2_fit_host",
 ]
 
 
@@ -179,6 +180,10 @@ def lib():
     if hasattr(L, "scde_knn_fit_dev"):  # (an SCDE_LIB build from before the mixture fit, in an A/B run, lacks it)
         L.scde_knn_fit_dev.argtypes = L.scde_knn_fit_host.argtypes = [P, P, i64, i, i, P, P, i, d, d, d, i, i, P, P, P,
                                                                       P, P, P]
+    if hasattr(L, "scde_nb2_fit_dev"):  # (likewise: a build from before scde.error.models)
+        L.scde_crossfit_inputs_dev.argtypes = L.scde_crossfit_inputs_host.argtypes = [P, P, i64, i, i, P, P, P, P, i,
+                                                                                      i, P, P, P]
+        L.scde_nb2_fit_dev.argtypes = L.scde_nb2_fit_host.argtypes = [P, P, i64, i, i, P, P, d, i, i, P, P, P, P, P, P]
     _lib = L
     return L
 

@@ -1,6 +1,9 @@
-// api_cluster.hip -- the host side of dist.hip, hclust.hip, olo.hip and tsne.hip: the cell-to-cell
-// distance measures, hierarchical clustering, optimal leaf ordering, exact t-SNE.  (engine.hip is
+// api_cluster.hip -- the host side of dist.hip, hclust.hip, olo.hip, tsne.hip, knn.hip, knn_fit.hip,
+// error_models.hip and nb2_fit.hip: the cell-to-cell distance measures, hierarchical clustering,
+// optimal leaf ordering, exact t-SNE, and the error-model fitters (knn.error.models,
+// scde.error.models).  (engine.hip is
 // the pipeline; a feature's host code lives in the api_ file named after its kernel files.)
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -674,64 +677,104 @@ int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int n
   return scde_knn_magnitudes_dev(ctx, dev, ngenes, ngenes, ncells, nb, kmax, ls, thr, trim, fpm, nabove);
 }
 
-// ------------------------------------------------------------------ knn.error.models' mixture fit
-// knn_fit.hip; contract in scde_hip.h.
-static int knn_fit_check(const double* fpm, const double* fail_prior, double theta_lo, double theta_hi, double awp,
-                         int max_iter, int lds_genes, const void* models, const void* iterations, const void* llh,
-                         const void* status) {
-  if (!fpm || !fail_prior || !models || !iterations || !llh || !status)
-    return fail(SCDE_EARG, "knn_fit: null argument");
-  if (!(theta_lo > 0.0) || !(theta_hi > theta_lo) || std::isinf(theta_hi))
-    return fail(SCDE_EARG, "knn_fit: the theta range must be 0 < lo < hi < Inf");
-  if (!std::isfinite(awp)) return fail(SCDE_EARG, "knn_fit: alpha_weight_power must be finite");
-  if (max_iter < 1) return fail(SCDE_EARG, "knn_fit: max_iter must be at least 1");
+// ------------------------------------------------------------------ the per-cell mixture fits
+// knn_fit.hip (knn.error.models; scde.error.models with linear.fit = TRUE) and nb2_fit.hip
+// (linear.fit = FALSE); contracts in scde_hip.h.
+static int fit_check(const char* who, const double* fpm, const double* fail_prior, int max_iter, int lds_genes,
+                     const void* models, const void* iterations, const void* llh, const void* status) {
+  if ((fpm == nullptr) != (fail_prior == nullptr) || !models || !iterations || !llh || !status)
+    return fail(SCDE_EARG, "%s: null argument", who);
+  if (max_iter < 1) return fail(SCDE_EARG, "%s: max_iter must be at least 1", who);
   if (lds_genes < 0 || lds_genes > knn_fit_lds_genes_max())
-    return fail(SCDE_EARG, "knn_fit: lds_genes must lie in [0, %d]", knn_fit_lds_genes_max());
+    return fail(SCDE_EARG, "%s: lds_genes must lie in [0, %d]", who, knn_fit_lds_genes_max());
   return SCDE_OK;
 }
 
-int scde_knn_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const double* fpm,
-                     const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
-                     double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
-                     double* llh, int* status, int* clusters, double* post) {
-  FORK_GUARD();
-  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "knn_fit"));
-  RCHK(knn_fit_check(fpm, fail_prior, theta_lo, theta_hi, alpha_weight_power, max_iter, lds_genes, models, iterations,
-                     llh, status));
-  const int N = ngenes, C = ncells;
+static int knn_fit_check(const double* fpm, const double* fail_prior, double theta_lo, double theta_hi, double awp,
+                         int max_iter, int lds_genes, const void* models, const void* iterations, const void* llh,
+                         const void* status) {
+  RCHK(fit_check("knn_fit", fpm, fail_prior, max_iter, lds_genes, models, iterations, llh, status));
+  if (!(theta_lo > 0.0) || !(theta_hi > theta_lo) || std::isinf(theta_hi))
+    return fail(SCDE_EARG, "knn_fit: the theta range must be 0 < lo < hi < Inf");
+  if (!std::isfinite(awp)) return fail(SCDE_EARG, "knn_fit: alpha_weight_power must be finite");
+  return SCDE_OK;
+}
+
+static int nb2_fit_check(const double* fpm, const double* fail_prior, double background_rate, int max_iter,
+                         int lds_genes, const void* models, const void* iterations, const void* llh,
+                         const void* status) {
+  RCHK(fit_check("nb2_fit", fpm, fail_prior, max_iter, lds_genes, models, iterations, llh, status));
+  if (!(background_rate > 0.0) || std::isinf(background_rate))
+    return fail(SCDE_EARG, "nb2_fit: background_rate must be a positive finite number");
+  return SCDE_OK;
+}
+
+// which fit, and its parameters
+struct CellFit {
+  bool nb2;
+  int local_theta;
+  double theta_lo, theta_hi, awp;  // knn_fit
+  double background_rate;          // nb2_fit
+};
+
+// Stages the inputs (or takes the resident ones of the last crossfit_inputs call when fpm and
+// fail_prior are null), sizes the workspace, launches the fit and brings the results back.
+static int cell_fit_dev(scde_ctx* ctx, const char* who, const CellFit& f, const int* counts_dev, int64_t ld, int N,
+                        int C, const double* fpm, const double* fail_prior, int max_iter, int lds_genes,
+                        double* models, int* iterations, double* llh, int* status, int* clusters, double* post) {
   const int cap = lds_genes > 0 ? lds_genes : 2048;
   long long nmax = 0;  // the largest cell's valid genes
-  for (int c = 0; c < C; ++c) {
-    long long n = 0;
-    const double* f = fail_prior + (size_t)c * N;
-    for (int g = 0; g < N; ++g) n += std::isnan(f[g]) ? 0 : 1;
-    nmax = std::max(nmax, n);
+  if (fail_prior) {
+    for (int c = 0; c < C; ++c) {
+      long long n = 0;
+      const double* p = fail_prior + (size_t)c * N;
+      for (int g = 0; g < N; ++g) n += std::isnan(p[g]) ? 0 : 1;
+      nmax = std::max(nmax, n);
+    }
   }
   RCHK(use_ctx(ctx));
+  if (!fail_prior) {
+    if (ctx->ci_n != N || ctx->ci_c != C)
+      return fail(SCDE_EARG, "%s: no resident inputs of %d genes x %d cells (the last were %d x %d)", who, N, C,
+                  ctx->ci_n, ctx->ci_c);
+    nmax = ctx->ci_nmax;
+  }
   int grid = 1;
-  HCHK(knn_fit_resident_groups(cap, &grid));
+  HCHK(f.nb2 ? nb2_fit_resident_groups(cap, &grid) : knn_fit_resident_groups(cap, &grid));
   grid = std::min(grid, C);
   const size_t nc = std::max<size_t>(1, (size_t)N * C);
   const size_t wsb = nmax > cap ? knn_fit_ws_bytes(nmax) * (size_t)grid : 0;
-  if (ctx->kf_fpm.ensure(sizeof(double) * nc) != hipSuccess || ctx->kf_fp.ensure(sizeof(double) * nc) != hipSuccess ||
+  if ((fail_prior && (ctx->kf_fpm.ensure(sizeof(double) * nc) != hipSuccess ||
+                      ctx->kf_fp.ensure(sizeof(double) * nc) != hipSuccess)) ||
       (wsb && ctx->kf_ws.ensure(wsb) != hipSuccess) ||
       (clusters && ctx->kf_cl.ensure(sizeof(int) * nc) != hipSuccess) ||
       (post && ctx->kf_post.ensure(sizeof(double) * nc) != hipSuccess))
-    return fail_oom("knn_fit: out of memory: %d x %d inputs and a workspace of %zu bytes", N, C, wsb);
+    return fail_oom("%s: out of memory: %d x %d inputs and a workspace of %zu bytes", who, N, C, wsb);
   HCHK(ctx->kf_models.ensure(sizeof(double) * 12 * (size_t)C));
   HCHK(ctx->kf_llh.ensure(sizeof(double) * (size_t)C));
   HCHK(ctx->kf_int.ensure(sizeof(int) * 2 * (size_t)C));
-  if (N > 0) {
-    HCHK(hipMemcpyAsync(ctx->kf_fpm.p, fpm, sizeof(double) * (size_t)N * C, hipMemcpyHostToDevice, ctx->stream));
-    HCHK(hipMemcpyAsync(ctx->kf_fp.p, fail_prior, sizeof(double) * (size_t)N * C, hipMemcpyHostToDevice,
-                        ctx->stream));
+  if (fail_prior) {
+    ctx->ci_n = ctx->ci_c = -1;  // (the staging buffers are the resident inputs' home)
+    if (N > 0) {
+      HCHK(hipMemcpyAsync(ctx->kf_fpm.p, fpm, sizeof(double) * (size_t)N * C, hipMemcpyHostToDevice, ctx->stream));
+      HCHK(hipMemcpyAsync(ctx->kf_fp.p, fail_prior, sizeof(double) * (size_t)N * C, hipMemcpyHostToDevice,
+                          ctx->stream));
+    }
   }
+  char* ws = wsb ? ctx->kf_ws.as<char>() : nullptr;
+  int* cl = clusters ? ctx->kf_cl.as<int>() : nullptr;
+  double* po = post ? ctx->kf_post.as<double>() : nullptr;
   hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
-  HCHK(launch_knn_fit(counts_dev, ld, N, C, ctx->kf_fpm.as<double>(), ctx->kf_fp.as<double>(), local_theta != 0,
-                      theta_lo, theta_hi, alpha_weight_power, max_iter, cap, wsb ? ctx->kf_ws.as<char>() : nullptr,
-                      nmax, grid, ctx->kf_models.as<double>(), ctx->kf_int.as<int>(), ctx->kf_llh.as<double>(),
-                      ctx->kf_int.as<int>() + C, clusters ? ctx->kf_cl.as<int>() : nullptr,
-                      post ? ctx->kf_post.as<double>() : nullptr, ctx->stream));
+  if (f.nb2)
+    HCHK(launch_nb2_fit(counts_dev, ld, N, C, ctx->kf_fpm.as<double>(), ctx->kf_fp.as<double>(), f.background_rate,
+                        std::log(f.background_rate), max_iter, cap, ws, nmax, grid, ctx->kf_models.as<double>(),
+                        ctx->kf_int.as<int>(), ctx->kf_llh.as<double>(), ctx->kf_int.as<int>() + C, cl, po,
+                        ctx->stream));
+  else
+    HCHK(launch_knn_fit(counts_dev, ld, N, C, ctx->kf_fpm.as<double>(), ctx->kf_fp.as<double>(), f.local_theta != 0,
+                        f.theta_lo, f.theta_hi, f.awp, max_iter, cap, ws, nmax, grid, ctx->kf_models.as<double>(),
+                        ctx->kf_int.as<int>(), ctx->kf_llh.as<double>(), ctx->kf_int.as<int>() + C, cl, po,
+                        ctx->stream));
   ctx->mark_end(SLOT_OTHER, ev);
   HCHK(hipMemcpyAsync(models, ctx->kf_models.p, sizeof(double) * 12 * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
   HCHK(hipMemcpyAsync(iterations, ctx->kf_int.p, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
@@ -746,6 +789,19 @@ int scde_knn_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngene
   return SCDE_OK;
 }
 
+int scde_knn_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const double* fpm,
+                     const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
+                     double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
+                     double* llh, int* status, int* clusters, double* post) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "knn_fit"));
+  RCHK(knn_fit_check(fpm, fail_prior, theta_lo, theta_hi, alpha_weight_power, max_iter, lds_genes, models, iterations,
+                     llh, status));
+  const CellFit f = {false, local_theta, theta_lo, theta_hi, alpha_weight_power, 0.0};
+  return cell_fit_dev(ctx, "knn_fit", f, counts_dev, ld, ngenes, ncells, fpm, fail_prior, max_iter, lds_genes, models,
+                      iterations, llh, status, clusters, post);
+}
+
 int scde_knn_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* fpm,
                       const double* fail_prior, int local_theta, double theta_lo, double theta_hi,
                       double alpha_weight_power, int max_iter, int lds_genes, double* models, int* iterations,
@@ -758,5 +814,157 @@ int scde_knn_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, 
   RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
   return scde_knn_fit_dev(ctx, dev, ngenes, ngenes, ncells, fpm, fail_prior, local_theta, theta_lo, theta_hi,
                           alpha_weight_power, max_iter, lds_genes, models, iterations, llh, status, clusters, post);
+}
+
+int scde_nb2_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const double* fpm,
+                     const double* fail_prior, double background_rate, int max_iter, int lds_genes, double* models,
+                     int* iterations, double* llh, int* status, int* clusters, double* post) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "nb2_fit"));
+  RCHK(nb2_fit_check(fpm, fail_prior, background_rate, max_iter, lds_genes, models, iterations, llh, status));
+  const CellFit f = {true, 0, 0.0, 0.0, 0.0, background_rate};
+  return cell_fit_dev(ctx, "nb2_fit", f, counts_dev, ld, ngenes, ncells, fpm, fail_prior, max_iter, lds_genes, models,
+                      iterations, llh, status, clusters, post);
+}
+
+int scde_nb2_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const double* fpm,
+                      const double* fail_prior, double background_rate, int max_iter, int lds_genes, double* models,
+                      int* iterations, double* llh, int* status, int* clusters, double* post) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "nb2_fit"));
+  RCHK(nb2_fit_check(fpm, fail_prior, background_rate, max_iter, lds_genes, models, iterations, llh, status));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_nb2_fit_dev(ctx, dev, ngenes, ngenes, ncells, fpm, fail_prior, background_rate, max_iter, lds_genes,
+                          models, iterations, llh, status, clusters, post);
+}
+
+// ------------------------------------------------------------------ scde.error.models' input stage
+// error_models.hip; contract in scde_hip.h.  The lists are checked before the GPU is touched: the
+// kernels index with them.
+struct CrossfitLists {
+  std::vector<int> ints;  // goff (ngroups + 1), members (C), need (C), poff (C + 1), part
+  int ngroups = 0;
+};
+
+static int crossfit_check(int ncells, const int* groups, const double* ls, const int* part_off,
+                          const int* part, int thr, int min_nonfailed, CrossfitLists* out) {
+  const int C = ncells;
+  if (!ls || !part_off) return fail(SCDE_EARG, "crossfit_inputs: null argument");
+  if (thr < 1) return fail(SCDE_EARG, "crossfit_inputs: thr must be at least 1");
+  if (min_nonfailed < 0) return fail(SCDE_EARG, "crossfit_inputs: min_nonfailed must not be negative");
+  for (int c = 0; c < C; ++c)
+    if (!(ls[c] > 0.0) || std::isinf(ls[c]))
+      return fail(SCDE_EARG, "crossfit_inputs: library size %d is not a positive finite number", c);
+  // groups in order of first appearance; members group by group, each in cell order
+  std::vector<int> code((size_t)C), first, size;
+  for (int c = 0; c < C; ++c) {
+    const int gc = groups ? groups[c] : 0;
+    size_t p = 0;
+    while (p < first.size() && first[p] != gc) ++p;
+    if (p == first.size()) {
+      if (p >= 4096) return fail(SCDE_EARG, "crossfit_inputs: more than 4096 groups");
+      first.push_back(gc);
+      size.push_back(0);
+    }
+    code[c] = (int)p;
+    ++size[p];
+  }
+  const int G = (int)first.size();
+  for (int p = 0; p < G; ++p)
+    if (size[p] < 2) return fail(SCDE_EARG, "crossfit_inputs: group %d has a single cell", first[p]);
+  if (part_off[0] != 0) return fail(SCDE_EARG, "crossfit_inputs: part_off must start at 0");
+  for (int c = 0; c < C; ++c)
+    if (part_off[c + 1] < part_off[c]) return fail(SCDE_EARG, "crossfit_inputs: part_off must not decrease");
+  const int P = part_off[C];
+  if (P > 0 && !part) return fail(SCDE_EARG, "crossfit_inputs: null argument");
+  std::vector<int> seen((size_t)C, -1);  // the last cell that listed each cell
+  for (int c = 0; c < C; ++c)
+    for (int k = part_off[c]; k < part_off[c + 1]; ++k) {
+      const int j = part[k];
+      if (j < 0 || j >= C || j == c || code[j] != code[c])
+        return fail(SCDE_EARG, "crossfit_inputs: partner %d of cell %d is not another cell of its group", j, c);
+      if (seen[j] == c) return fail(SCDE_EARG, "crossfit_inputs: cell %d lists partner %d twice", c, j);
+      seen[j] = c;
+    }
+  std::vector<int>& v = out->ints;
+  v.assign((size_t)(G + 1) + C + C + (C + 1) + P, 0);
+  int* goff = v.data();
+  int* members = goff + G + 1;
+  int* need = members + C;
+  int* poff = need + C;
+  int* pl = poff + C + 1;
+  for (int p = 0; p < G; ++p) goff[p + 1] = goff[p] + size[p];
+  std::vector<int> at(goff, goff + G);
+  for (int c = 0; c < C; ++c) {
+    members[at[code[c]]++] = c;
+    need[c] = std::min(size[code[c]] - 1, min_nonfailed);
+  }
+  for (int c = 0; c <= C; ++c) poff[c] = part_off[c];
+  for (int k = 0; k < P; ++k) pl[k] = part[k];
+  out->ngroups = G;
+  return SCDE_OK;
+}
+
+int scde_crossfit_inputs_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const int* groups, const double* ls, const int* part_off, const int* part, int thr,
+                             int min_nonfailed, double* fpm, double* fail_prior, int* nabove) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "crossfit_inputs"));
+  CrossfitLists L;
+  RCHK(crossfit_check(ncells, groups, ls, part_off, part, thr, min_nonfailed, &L));
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells, G = L.ngroups;
+  ctx->ci_n = ctx->ci_c = -1;
+  const size_t nc = std::max<size_t>(1, (size_t)N * C);
+  if (ctx->kf_fpm.ensure(sizeof(double) * nc) != hipSuccess || ctx->kf_fp.ensure(sizeof(double) * nc) != hipSuccess ||
+      ctx->ci_nab.ensure(sizeof(int) * nc) != hipSuccess)
+    return fail_oom("crossfit_inputs: out of memory: the %d x %d results need %zu bytes of device memory", N, C,
+                    20 * nc);
+  // the lists, then the cells' valid-gene counters
+  const size_t li = L.ints.size();
+  L.ints.resize(li + (size_t)C, 0);
+  RCHK(upload(ctx, ctx->ci_int, L.ints.data(), sizeof(int) * L.ints.size()));
+  RCHK(upload(ctx, ctx->ci_ls, ls, sizeof(double) * (size_t)C));
+  const int* goff = ctx->ci_int.as<int>();
+  const int* members = goff + G + 1;
+  const int* need = members + C;
+  const int* poff = need + C;
+  const int* pl = poff + C + 1;
+  int* nvalid = ctx->ci_int.as<int>() + li;
+  std::vector<int> nv((size_t)C, 0);
+  if (N > 0) {
+    hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+    HCHK(launch_crossfit_inputs(counts_dev, ld, N, C, G, goff, members, need, poff, pl, ctx->ci_ls.as<double>(), thr,
+                                ctx->kf_fpm.as<double>(), ctx->kf_fp.as<double>(), ctx->ci_nab.as<int>(), nvalid,
+                                ctx->stream));
+    ctx->mark_end(SLOT_OTHER, ev);
+    HCHK(hipMemcpyAsync(nv.data(), nvalid, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t db = sizeof(double) * (size_t)N * C;
+    if (fpm) HCHK(hipMemcpyAsync(fpm, ctx->kf_fpm.p, db, hipMemcpyDeviceToHost, ctx->stream));
+    if (fail_prior) HCHK(hipMemcpyAsync(fail_prior, ctx->kf_fp.p, db, hipMemcpyDeviceToHost, ctx->stream));
+    if (nabove)
+      HCHK(hipMemcpyAsync(nabove, ctx->ci_nab.p, sizeof(int) * (size_t)N * C, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  RCHK(ctx->sync());
+  long long nmax = 0;
+  for (int c = 0; c < C; ++c) nmax = std::max<long long>(nmax, nv[c]);
+  ctx->ci_nmax = nmax;
+  ctx->ci_n = N;
+  ctx->ci_c = C;
+  return SCDE_OK;
+}
+
+int scde_crossfit_inputs_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const int* groups, const double* ls, const int* part_off, const int* part, int thr,
+                              int min_nonfailed, double* fpm, double* fail_prior, int* nabove) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "crossfit_inputs"));
+  CrossfitLists L;
+  RCHK(crossfit_check(ncells, groups, ls, part_off, part, thr, min_nonfailed, &L));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_crossfit_inputs_dev(ctx, dev, ngenes, ngenes, ncells, groups, ls, part_off, part, thr, min_nonfailed,
+                                  fpm, fail_prior, nabove);
 }
 }  // extern "C"

@@ -168,6 +168,34 @@ __device__ inline double dpois_log(double x, double lambda) {
 
 __device__ __noinline__ double dpois_log_cold(double x, double lambda) { return dpois_log(x, lambda); }
 
+// digamma and trigamma for x > 0 (MASS::theta.ml's score and information, nb2_fit.hip): the
+// recurrence psi(x) = psi(x + 1) - 1 / x (psi1(x) = psi1(x + 1) + 1 / x^2) upward to x >= 12, then
+// the asymptotic series through the B14 term (the next one is below 3e-18 there).  Checked against
+// a library digamma / trigamma on [1e-2, 1.6e5]: 9e-16 of max(1, |psi|) and 7e-16 relative.
+__device__ inline double digamma_pos(double x) {
+  double s = 0.0;
+  while (x < 12.0) {
+    s += 1.0 / x;
+    x += 1.0;
+  }
+  const double r = 1.0 / x, r2 = r * r;
+  const double p =
+      r2 * (1.0 / 12 -
+            r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 - r2 * (691.0 / 32760 - r2 * (1.0 / 12)))))));
+  return log(x) - 0.5 * r - p - s;
+}
+
+__device__ inline double trigamma_pos(double x) {
+  double s = 0.0;
+  while (x < 12.0) {
+    s += 1.0 / (x * x);
+    x += 1.0;
+  }
+  const double r = 1.0 / x, r2 = r * r;
+  return s + r + 0.5 * r2 +
+         r * r2 * (1.0 / 6 - r2 * (1.0 / 30 - r2 * (1.0 / 42 - r2 * (1.0 / 30 - r2 * (5.0 / 66 - r2 * (691.0 / 2730 - r2 * (7.0 / 6)))))));
+}
+
 // R qnorm(p, 0, 1, lower_tail, log.p = FALSE): Wichura's AS241 (PPND16)
 __device__ inline double qnorm(double p, bool lower_tail) {
   if (isnan(p)) return p;

@@ -258,6 +258,12 @@ struct scde_ctx {
   // knn.error.models' mixture fit: fpm and the starting posteriors staged, the workspace of the
   // cells too large for LDS, the results before they go to the host
   Buf kf_fpm, kf_fp, kf_ws, kf_models, kf_int, kf_llh, kf_cl, kf_post;
+  // scde.error.models' input stage: the group and partner lists, nabove; its fpm and fail_prior
+  // land in kf_fpm / kf_fp and stay there for a fit (ci_n x ci_c, the largest cell has ci_nmax
+  // valid genes; ci_n = -1: nothing resident)
+  Buf ci_int, ci_ls, ci_nab;
+  int ci_n = -1, ci_c = -1;
+  long long ci_nmax = 0;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters

@@ -587,6 +587,25 @@ hipError_t launch_knn_fit(const int* counts, long long ld, int N, int C, const d
                           char* ws, long long ws_cap, int grid, double* models, int* iters, double* llh, int* status,
                           int* clusters, double* post, hipStream_t s);
 
+// ---- scde.error.models' input stage (error_models.hip; contract in include/scde_hip.h).  counts
+// N x C column-major (ld); fpm, fp, nabove dense N x C.  goff (ngroups + 1) cuts members (the
+// cells, group by group, each group in cell order); need: per cell, the nabove a valid gene has
+// at least; poff (C + 1) cuts part, every cell's cross-fit partners; nvalid (C, zeroed by the
+// caller) receives every cell's number of valid genes.  Every group has at least two cells.
+hipError_t launch_crossfit_inputs(const int* counts, long long ld, int N, int C, int ngroups, const int* goff,
+                                  const int* members, const int* need, const int* poff, const int* part,
+                                  const double* ls, int thr, double* fpm, double* fp, int* nabove, int* nvalid,
+                                  hipStream_t s);
+
+// ---- scde.error.models' mixture fit with linear.fit = FALSE (nb2_fit.hip; contract in
+// include/scde_hip.h).  Arguments, LDS and workspace as launch_knn_fit's (knn_fit_lds_bytes,
+// knn_fit_ws_bytes); log_background_rate is written to the models as fail.r.
+hipError_t nb2_fit_resident_groups(int lds_genes, int* groups);
+hipError_t launch_nb2_fit(const int* counts, long long ld, int N, int C, const double* fpm, const double* fp,
+                          double background_rate, double log_background_rate, int max_iter, int lds_genes, char* ws,
+                          long long ws_cap, int grid, double* models, int* iters, double* llh, int* status,
+                          int* clusters, double* post, hipStream_t s);
+
 // ---- pagoda.top.aspects' matrix step (top_aspects.hip; contract in include/scde_hip.h).  x, w,
 // xv, xvw: m x C row-major (an aspect contiguous); num: m values.  Row r of xv is x's row centred
 // times num[r] / sqrt(its variance, denominator C - 1), row r of xvw is w's row over its sum

@@ -13,9 +13,12 @@ and the fit itself (csrc/knn_fit.hip).
   * ``knn_error_models``          the whole function: R's joint model matrix ``jmm``
 
 The fit is the project's statement of flexmix's EM, compared with R's
-stored result on the pollen data (tests/test_gpu_knn_fit.py); ``linear_fit=False``
-(fit.nb2.mixture.model) is not built.  ``counts`` is an integer genes x cells matrix or a resident
-``DeviceCounts``; ``thr`` is min.count.threshold and an entry is valid when ``counts >= thr``.
+stored result on the pollen data (tests/test_gpu_knn_fit.py).  ``linear_fit=False``
+(fit.nb2.mixture.model with ``prior = cp``) is ``error_models.nb2_fit_models`` on
+``knn_model_inputs``' result (csrc/nb2_fit.hip); ``knn_fit_models`` and
+``knn_error_models`` themselves still refuse it.  ``counts`` is an integer genes x cells matrix or
+a resident ``DeviceCounts``; ``thr`` is min.count.threshold and an entry is valid when
+``counts >= thr``.
 The TMM factors are written from Robinson & Oshlack (2010) with edgeR's documented defaults and
 were not checked against edgeR; ``norm_factors=`` / ``library_sizes=`` take a caller's values.
 """
@@ -365,27 +368,16 @@ FIT_STATUS = {0: "ok", 1: "fewer than 3 valid genes", 2: "no weight on the corre
               3: "a parameter or the likelihood is not finite"}
 
 
-def knn_fit_models(inputs, counts, local_theta_fit=None, theta_fit_range=(1e-2, 1e2), alpha_weight_power=0.5,
-                   iter=50, linear_fit=True, return_details=False, lds_genes=0, ctx: api.Context | None = None):
-    """The per-cell EM mixture fit (fit.nb2gth.mixture.model + get.compressed.v1.model; contract in
-    include/scde_hip.h and DESIGN.md section 4.15) on what ``knn_model_inputs`` returned.
-
-    Returns the cells x 12 model matrix in ``models.MODEL_COLUMNS``' order (a failed cell's row is
-    NaN; without local theta the ``corr.ltheta.*`` columns are NaN), and with ``return_details`` a
-    dict as well: ``iterations``, ``llh``, ``status`` (per cell; ``FIT_STATUS``), ``clusters``
-    (genes x cells int32: 1 / 2, R's ``clusters(m1)``, 0 outside the valid genes) and
-    ``posteriors`` (genes x cells: the failed component's final posterior, NaN outside).
-    ``local_theta_fit`` defaults to True, as in R; ``iter = 1`` is one M-step and one E-step from the
-    starting posteriors.  ``lds_genes`` is the C entry's (0: its default)."""
-    if not linear_fit:
-        raise NotImplementedError("linear_fit = False (fit.nb2.mixture.model) is not built")
-    local = True if local_theta_fit is None else bool(local_theta_fit)
-    lo, hi = (float(v) for v in theta_fit_range)
+def _fit_call(kind, inputs, counts, params, iter, return_details, lds_genes, ctx):
+    """One call of scde_knn_fit_* (``kind`` "knn") or scde_nb2_fit_* ("nb2") with the fit's own
+    ``params``; ``inputs`` None: the inputs scde_crossfit_inputs_* left resident in the context."""
     dc, mat, N, C = _counts_arg(counts)
-    fpm = np.asfortranarray(inputs["fpm"], dtype=np.float64)
-    fp = np.asfortranarray(inputs["fail_prior"], dtype=np.float64)
-    if fpm.shape != (N, C) or fp.shape != (N, C):
-        raise ValueError("inputs do not belong to these counts")
+    fpm = fp = None
+    if inputs is not None:
+        fpm = np.asfortranarray(inputs["fpm"], dtype=np.float64)
+        fp = np.asfortranarray(inputs["fail_prior"], dtype=np.float64)
+        if fpm.shape != (N, C) or fp.shape != (N, C):
+            raise ValueError("inputs do not belong to these counts")
     models = np.zeros((C, 12), order="F")
     its = np.zeros(C, np.int32)
     status = np.zeros(C, np.int32)
@@ -393,15 +385,37 @@ def knn_fit_models(inputs, counts, local_theta_fit=None, theta_fit_range=(1e-2, 
     cl = np.zeros((N, C), np.int32, order="F") if return_details else None
     post = np.zeros((N, C), order="F") if return_details else None
     h = _handle(dc, ctx)
-    args = (N, N, C, api._p(fpm), api._p(fp), int(local), lo, hi, float(alpha_weight_power), int(iter),
-            int(lds_genes), api._p(models), api._p(its), api._p(llh), api._p(status), api._p(cl), api._p(post))
-    if dc is not None:
-        check(lib().scde_knn_fit_dev(h, dc.ptr, *args))
-    else:
-        check(lib().scde_knn_fit_host(h, api._p(mat), *args))
+    args = (N, N, C, api._p(fpm), api._p(fp), *params, int(iter), int(lds_genes), api._p(models), api._p(its),
+            api._p(llh), api._p(status), api._p(cl), api._p(post))
+    fn = {("knn", True): "scde_knn_fit_dev", ("knn", False): "scde_knn_fit_host", ("nb2", True): "scde_nb2_fit_dev",
+          ("nb2", False): "scde_nb2_fit_host"}[kind, dc is not None]
+    check(getattr(lib(), fn)(h, dc.ptr if dc is not None else api._p(mat), *args))
     if not return_details:
         return models
     return models, {"iterations": its, "llh": llh, "status": status, "clusters": cl, "posteriors": post}
+
+
+def knn_fit_models(inputs, counts, local_theta_fit=None, theta_fit_range=(1e-2, 1e2), alpha_weight_power=0.5,
+                   iter=50, linear_fit=True, return_details=False, lds_genes=0, ctx: api.Context | None = None):
+    """The per-cell EM mixture fit (fit.nb2gth.mixture.model + get.compressed.v1.model; contract in
+    include/scde_hip.h and DESIGN.md section 4.15) on what ``knn_model_inputs`` (or
+    ``error_models.error_model_inputs``) returned.
+
+    Returns the cells x 12 model matrix in ``models.MODEL_COLUMNS``' order (a failed cell's row is
+    NaN; without local theta the ``corr.ltheta.*`` columns are NaN), and with ``return_details`` a
+    dict as well: ``iterations``, ``llh``, ``status`` (per cell; ``FIT_STATUS``), ``clusters``
+    (genes x cells int32: 1 / 2, R's ``clusters(m1)``, 0 outside the valid genes) and
+    ``posteriors`` (genes x cells: the failed component's final posterior, NaN outside).
+    ``local_theta_fit`` defaults to True, as in R; ``iter = 1`` is one M-step and one E-step from the
+    starting posteriors.  ``lds_genes`` is the C entry's (0: its default).  ``linear_fit=False``
+    (fit.nb2.mixture.model) is a function of its own, ``error_models.nb2_fit_models``, which takes
+    the same inputs."""
+    if not linear_fit:
+        raise NotImplementedError("linear_fit = False is error_models.nb2_fit_models (fit.nb2.mixture.model)")
+    local = True if local_theta_fit is None else bool(local_theta_fit)
+    lo, hi = (float(v) for v in theta_fit_range)
+    return _fit_call("knn", inputs, counts, (int(local), lo, hi, float(alpha_weight_power)), iter, return_details,
+                     lds_genes, ctx)
 
 
 def knn_error_models(counts, groups=None, k=None, min_nonfailed=5, min_count_threshold=1, min_size_entries=2000,
@@ -420,7 +434,8 @@ def knn_error_models(counts, groups=None, k=None, min_nonfailed=5, min_count_thr
 
     from .models import MODEL_COLUMNS
     if not linear_fit:
-        raise NotImplementedError("linear_fit = False (fit.nb2.mixture.model) is not built")
+        raise NotImplementedError("linear_fit = False is not built here: error_models.nb2_fit_models takes "
+                                  "knn_model_inputs' result")
     local = True if local_theta_fit is None else bool(local_theta_fit)
     cells = None if isinstance(counts, api.DeviceCounts) else api._counts_matrix(counts)[2]
     inputs = knn_model_inputs(counts, groups=groups, k=k, min_nonfailed=min_nonfailed,
