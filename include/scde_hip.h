@@ -201,7 +201,11 @@ int scde_ctx_reset_kernel_times(scde_ctx* ctx);
  * the bootstrap kernel of the last posterior (0 k_boot2, 1 k_boot_tiles / k_boot_gene, 3 the
  * general k_boot); "stream_syncs", "arena_syncs" (this context's and its peer's streams drained
  * by a buffer regrowth / a pinned arena wrap) and "buf_reallocs" (process-wide workspace
- * reallocations, each a hipFree): 0 in steady state. */
+ * reallocations, each a hipFree): 0 in steady state; "ratio_n_max": the constant largest n
+ * (grid points of one row) of scde_matSlideMult, scde_ratio_summary and scde_distribution_summary
+ * (m = 2n - 1), whose kernel keeps a gene's rows in LDS ("ratio_n_lds64": the largest n that
+ * needs no more than the 64 KiB a launch gets without opting in).  A larger n, a DE grid above it, or a
+ * batch-corrected DE grid with 2 * ngrid - 1 above it, is refused with SCDE_EARG. */
 /* Options can also come from the environment: SCDE_OPTIONS="name=value,..." is applied to every
  * context as it is created (an unknown name fails the creation). */
 int scde_ctx_set_option(scde_ctx* ctx, const char* name, double value);

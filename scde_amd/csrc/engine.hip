@@ -1566,6 +1566,8 @@ int scde_ctx_get_stat(scde_ctx* ctx, const char* name, double* value) {
   else if (n == "skip_kept") *value = ctx->st_skip_kept;
   else if (n == "boot_f64_fma") *value = ctx->st_boot_f64_fma;
   else if (n == "boot_path") *value = ctx->st_boot_path;
+  else if (n == "ratio_n_max") *value = ratio_n_max();  // constants: the largest n of the ratio entries,
+  else if (n == "ratio_n_lds64") *value = ratio_n_default_lds();  // and the largest within 64 KiB of LDS
   else if (n == "skip_redo") *value = ctx->st_skip_redo;
   else if (n == "pair_redo") *value = ctx->st_pair_redo;
   else if (n == "degen") *value = ctx->st_degen;
@@ -1884,10 +1886,18 @@ int scde_jpmatLogBatchBoot(const double* const* mats, const int* type_off, const
   return jpmat_common(mats, type_off[ntypes], type_off, comp, ntypes, nrows, ncols, nboot, seed, out);
 }
 
+// k_ratio_summary holds a gene's rows and outputs in LDS: n above ratio_n_max() cannot be launched
+static int ratio_n_check(const char* who, int n) {
+  if (n > ratio_n_max())
+    return fail(SCDE_EARG, "%s: n = %d grid points; the ratio posterior supports at most n = %d", who, n, ratio_n_max());
+  return SCDE_OK;
+}
+
 static int ratio_common(const double* pmat1, const double* pmat2, int nrows, int n, const double* prior_y,
                         const double* diffv, int zi, int normalize, double* ratio, double* res) {
   if (!pmat1 || !pmat2 || nrows < 0 || n <= 0) return fail(SCDE_EARG, "bad ratio arguments");
   if (res && (!diffv || zi < 0 || zi >= 2 * n - 1)) return fail(SCDE_EARG, "bad diffv/zi");
+  RCHK(ratio_n_check(normalize ? "scde_ratio_summary" : "scde_matSlideMult", n));
   scde_ctx* cx = nullptr;
   RCHK(use_ctx(cx));
   hipStream_t st = cx->stream;
@@ -1928,6 +1938,7 @@ int scde_distribution_summary(const double* rpost, int nrows, int m, const doubl
   FORK_GUARD();
   if (!rpost || !diffv || !res || nrows < 0 || m < 1 || (m % 2) == 0) return fail(SCDE_EARG, "bad summary arguments");
   if (zi < 0 || zi >= m) return fail(SCDE_EARG, "zi out of range");
+  RCHK(ratio_n_check("scde_distribution_summary", (m + 1) / 2));
   scde_ctx* cx = nullptr;
   RCHK(use_ctx(cx));
   hipStream_t st = cx->stream;
@@ -2499,6 +2510,7 @@ static int de_run(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, 
   if (!ctx || !counts_dev || !p || !p->models || !p->groups || !p->prior_x || !p->prior_y)
     return fail(SCDE_EARG, "null argument");
   if (ngenes < 0 || p->ncells <= 0 || p->ngrid <= 1) return fail(SCDE_EARG, "bad dimensions");
+  RCHK(ratio_n_check("scde_expression_difference", p->ngrid));
   HCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int C = p->ncells, G = p->ngrid;
@@ -2728,6 +2740,10 @@ int scde_expression_difference_batch_dev(scde_ctx* ctx, const int* counts_dev, i
       !results)
     return fail(SCDE_EARG, "null argument");
   if (ngenes < 0 || p->ncells <= 0 || p->ngrid <= 1 || nbatch < 1) return fail(SCDE_EARG, "bad dimensions");
+  // (the second-level ratio runs over the 2 G - 1 columns of the first)
+  if (p->ngrid > (ratio_n_max() + 1) / 2)
+    return fail(SCDE_EARG, "scde_expression_difference_batch: %d grid points; the batch-adjusted ratio posterior "
+                "(n = 2 * ngrid - 1) supports at most n = %d", p->ngrid, ratio_n_max());
   HCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int C = p->ncells, G = p->ngrid, N = ngenes;
@@ -2937,6 +2953,7 @@ int scde_expression_difference_host(scde_ctx* ctx, const int* counts, int64_t ld
                                     double* ratio) {
   FORK_GUARD();
   if (!p || !p->groups) return fail(SCDE_EARG, "null argument");
+  RCHK(ratio_n_check("scde_expression_difference", p->ngrid));  // before the counts are staged
   RCHK(use_ctx(ctx));
   if (!counts) return fail(SCDE_EARG, "null argument");
   const int C = p->ncells;
@@ -2982,6 +2999,9 @@ int scde_expression_difference_batch_host(scde_ctx* ctx, const int* counts, int6
                                           double* jp2, double* ratio, double* adj_ratio, double* batch_ratio) {
   FORK_GUARD();
   if (!p) return fail(SCDE_EARG, "null argument");
+  if (p->ngrid > (ratio_n_max() + 1) / 2)  // before the counts are staged
+    return fail(SCDE_EARG, "scde_expression_difference_batch: %d grid points; the batch-adjusted ratio posterior "
+                "(n = 2 * ngrid - 1) supports at most n = %d", p->ngrid, ratio_n_max());
   const int* dev = nullptr;
   RCHK(stage_counts(ctx, counts, ld, ngenes, p->ncells, &dev));
   return scde_expression_difference_batch_dev(ctx, dev, ngenes, ngenes, p, batch_models, batch_codes, nbatch,

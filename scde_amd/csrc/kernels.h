@@ -340,6 +340,12 @@ hipError_t launch_prior_tail(double tot_mass, double max_value, double bw, int L
                              const unsigned long long* hist, double* work, double* out, hipStream_t s);
 hipError_t launch_sort_doubles(const double* in, double* out, long long n, void* work, size_t* work_bytes,
                                hipStream_t s);
+// k_ratio_summary keeps both rows (twice) and the 2n-1 outputs in dynamic LDS: above 64 KiB
+// the launcher opts in, above the 160 KiB of a workgroup it returns hipErrorInvalidValue
+// without launching.  ratio_n_max() is the largest n that fits (callers refuse a larger one).
+size_t ratio_lds_bytes(int n);
+int ratio_n_max();
+int ratio_n_default_lds();  // the largest n that launches without the opt-in
 hipError_t launch_ratio_summary(const RatioArgs& a, hipStream_t s);
 
 

@@ -84,6 +84,18 @@ __device__ __forceinline__ void slide_group(const double* __restrict__ A, const 
   }
 }
 
+// One output, summed over exactly its own n - |s| terms (slide_group's straddling form).  For
+// rows with a NaN, an infinity or a negative entry, where a padded term is not +0 (inf * 0 =
+// NaN) and so no lag may run past its own length.
+__device__ __forceinline__ double slide_one(const double* A, const double* B, int n, int s) {
+  const int o1 = s > 0 ? s : 0, o2 = s < 0 ? -s : 0;
+  const int len = n - (s < 0 ? -s : s);
+  double acc = 0.0;
+#pragma unroll 1
+  for (int t = 0; t < len; ++t) acc = __dadd_rn(acc, __dmul_rn(A[t + o1], B[t + o2]));
+  return acc;
+}
+
 // Both sides of the slide in one form: X(d) = sum_t P[t] Q[t + d], t ascending, for R
 // adjacent lags d = d0 .. d0+R-1 (s >= 0: P = B, Q = A, d = s; s < 0: P = A, Q = B,
 // d = -s), so every lane runs the same instruction stream whichever side its group is on.
@@ -210,6 +222,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCDE_RATIO_
     }
     __syncthreads();
     int al = 0, ah = 1 << 30, bl = 0, bh = 1 << 30;
+    // a row with a NaN, an infinity or a negative entry: every lag over exactly its own terms
+    const bool exact = !a.xin && sup[4];
     if (!a.xin && !sup[4]) {
       al = sup[0];
       ah = sup[1];
@@ -220,7 +234,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCDE_RATIO_
     // s = o - (n-1), t ascending, each product and sum rounded separately.
     dd ls = {0.0, 0.0};
     for (int o = tid; o < m && a.xin; o += blockDim.x) X[o] = a.xin[(long long)g * a.xg + (long long)o * a.xo];
-    if (!a.xin && !(SCDE_RATIO_DIAG & 1)) {
+    if (exact && !(SCDE_RATIO_DIAG & 1)) {
+      // (block-uniform: sup[] is in LDS) one output per thread, the longest in the middle
+      for (int o = tid; o < m; o += blockDim.x) {
+        const double v = slide_one(A, B, n, o - (n - 1));
+        X[o] = v;
+        ls = dd_add_d(ls, v);
+      }
+    } else if (!a.xin && !(SCDE_RATIO_DIAG & 1)) {
       const int side = nw >= 2 ? (wid & 1) : 0;
       const int wstep = nw >= 2 ? 64 * (nw >> 1) : 64;
       for (int pass = 0; pass < (nw >= 2 ? 1 : 2); ++pass) {
@@ -276,8 +297,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCDE_RATIO_
     dd tot = {red[0], red2[0]};
     for (int w = 1; w < nw; ++w) tot = dd_add(tot, dd{red[w], red2[w]});
     const bool norm = a.normalize && !a.xin;
-    const double rs = norm ? dd_to_d(tot) : 1.0;
+    double rs = norm ? dd_to_d(tot) : 1.0;
     __syncthreads();
+    if (norm && !isfinite(rs)) {
+      // An infinite or NaN output (or an overflowing sum) leaves the double-double sum NaN
+      // (inf - inf in its error term), where the reference's long double sum is +-inf unless a
+      // NaN or both infinities take part.  A plain sum of the outputs tells the three apart; the
+      // order of its terms does not matter to that.  (block-uniform branch: rs is the same in
+      // every thread)
+      double ps = 0.0;
+      for (int o = tid; o < m; o += blockDim.x) ps += X[o];
+      for (int d = 32; d >= 1; d >>= 1) ps += __shfl_xor(ps, d, 64);
+      if (lane == 0) red[wid] = ps;
+      __syncthreads();
+      rs = red[0];
+      for (int w = 1; w < nw; ++w) rs += red[w];
+      __syncthreads();
+    }
     for (int o = tid; o < m; o += blockDim.x) {
       const double p = norm ? X[o] / rs : X[o];
       X[o] = p;
@@ -424,12 +460,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCDE_RATIO_
 }
 
 // ================================================================== launchers
+namespace {
+constexpr size_t kRatioLdsDefault = 64 * 1024;  // what a launch may ask for without opting in
+constexpr size_t kRatioLdsMax = 160 * 1024;     // LDS of one gfx950 workgroup
+}  // namespace
+
+// the kernel's dynamic LDS (its layout comment): A, B, A1, B1, X + scratch, red, red2, 32 ints
+size_t ratio_lds_bytes(int n) {
+  const size_t NA = ((size_t)n + 9) & ~(size_t)1;
+  return sizeof(double) * (4 * NA + 2 + ((2 * (size_t)n - 1 + 49) & ~(size_t)1) + 16) + sizeof(int) * 32;
+}
+
+static int ratio_n_within(size_t bytes) {
+  int n = (int)(bytes / (6 * sizeof(double)));  // 6 doubles per point: above the answer
+  while (n > 1 && ratio_lds_bytes(n) > bytes) --n;
+  return n;
+}
+
+int ratio_n_max() { return ratio_n_within(kRatioLdsMax); }
+
+int ratio_n_default_lds() { return ratio_n_within(kRatioLdsDefault); }
+
 hipError_t launch_ratio_summary(const RatioArgs& a, hipStream_t s) {
   if (a.ngenes <= 0) return hipSuccess;
-  const int NA = (a.n + 9) & ~1;
-  const size_t shm = sizeof(double) * (size_t)(4 * NA + 2 + ((2 * a.n - 1 + 49) & ~1) + 16) + sizeof(int) * 32;
+  if (a.n < 1 || a.n > ratio_n_max()) return hipErrorInvalidValue;
+  const size_t shm = ratio_lds_bytes(a.n);
   // R = 4: a 4-step unrolled loop rotates the R-wide register window fully (no moves);
   // measured fastest of R = 4, 5, 8 at n = 401, in blocks of 128 threads
+  if (shm > kRatioLdsDefault) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_ratio_summary<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)shm);
+    if (e != hipSuccess) return e;
+  }
   const int grid = a.ngenes < 65536 ? a.ngenes : 65536;
   hipLaunchKernelGGL(k_ratio_summary<4>, dim3(grid), dim3(128), shm, s, a);
   return hipGetLastError();
