@@ -582,6 +582,32 @@ int scde_hclust_dev(scde_ctx* ctx, const double* d_dev, int64_t ld, int n, int m
 int scde_hclust_batch_dev(scde_ctx* ctx, int nprob, const double* d_dev, const int64_t* off, const int* n,
                           int method, int* merge, double* height, int* order);
 
+/* ---------------------------------------------------------------- stats::dist
+ * R's dist(x, method) between the rows of x (csrc/rdist.hip), so that hclust(dist(x)) needs no
+ * host step.  Stated from R's documentation and from how its C loop reads; not checked against
+ * a run of R.
+ *
+ * Input.  x: n x p doubles, column-major (R's layout), ld >= n, n >= 1, p >= 0.  method:
+ * 0 euclidean, 1 manhattan, 2 maximum; any other code is SCDE_EARG.
+ *
+ * One pair (i, j), i != j.  The columns are walked in increasing order.  With
+ * d = x(i, k) - x(j, k), column k takes part when d is not NaN: a NaN in either value and
+ * Inf - Inf drop out.  count is the number of columns that took part.  All float64, each
+ * operation rounded on its own (no fused multiply-add), the sum evaluated left to right from 0:
+ *   euclidean   s += d * d;  count == 0: NaN;  count != p: s = s / ((double)count / p);  sqrt(s)
+ *   manhattan   s += |d|;    count == 0: NaN;  count != p: s = s / ((double)count / p);  s
+ *   maximum     the largest |d|;  count == 0: NaN;  no scaling
+ * The result equals that evaluation bit for bit, whatever the tiling: a pair's sum has one
+ * order, and (a - b)^2 == (b - a)^2 exactly, so out(i, j) and out(j, i) hold the same bits.
+ *
+ * Output.  n x n doubles, column-major, ld = n, both triangles, the diagonal exactly 0: what
+ * scde_hclust_* takes.  A NaN distance (no common column) is written as it is; hclust then
+ * refuses the matrix.  No atomics: results repeat bit for bit, and the two entries agree bit for
+ * bit.  ctx may be NULL. */
+int scde_dist_host(scde_ctx* ctx, const double* x, int64_t ld, int n, int p, int method, double* out);
+/* x_dev and out_dev are resident in HBM (out_dev: n * n doubles, not overlapping x_dev). */
+int scde_dist_dev(scde_ctx* ctx, const double* x_dev, int64_t ld, int n, int p, int method, double* out_dev);
+
 /* ---------------------------------------------------------------- optimal leaf ordering
  * cba::order.optimal(dist, merge), the step of pagoda.cluster.cells after hclust
  * (R/functions.R:2668-2672): among the 2^(n-1) orientations of the tree, the one whose

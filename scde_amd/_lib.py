@@ -43,6 +43,7 @@ EXPORTS = [
     "scde_knn_similarity_dev", "scde_knn_similarity_host", "scde_knn_neighbours",
     "scde_knn_magnitudes_dev", "scde_knn_magnitudes_host", "scde_knn_fit_dev", "scde_knn_fit_host",
     "scde_crossfit_inputs_dev", "scde_crossfit_inputs_host", "scde_nb2_fit_dev", "scde_nb2_fit_host",
+    "scde_dist_host", "scde_dist_dev",
 ]
 
 
@@ -184,6 +185,8 @@ def lib():
         L.scde_crossfit_inputs_dev.argtypes = L.scde_crossfit_inputs_host.argtypes = [P, P, i64, i, i, P, P, P, P, i,
                                                                                       i, P, P, P]
         L.scde_nb2_fit_dev.argtypes = L.scde_nb2_fit_host.argtypes = [P, P, i64, i, i, P, P, d, i, i, P, P, P, P, P, P]
+    if hasattr(L, "scde_dist_dev"):  # (likewise: a build from before stats::dist)
+        L.scde_dist_host.argtypes = L.scde_dist_dev.argtypes = [P, P, i64, i, i, i, P]
     _lib = L
     return L
 

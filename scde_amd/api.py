@@ -498,6 +498,96 @@ def _expression_difference_batch(models, mat, genes, prior, codes, batch, nrand,
     return out
 
 
+def _group_levels(groups):
+    """The two level names of a groups factor, in factor order (``_groups_vector``'s rule)."""
+    if hasattr(groups, "cat") and hasattr(groups, "index"):
+        return [str(x) for x in groups.cat.categories]
+    return [str(x) for x in sorted(set(x for x in groups if x is not None and x == x))]
+
+
+def scde_test_gene_expression_difference(gene, models, counts, prior, groups=None, batch=None, batch_models=None,
+                                         n_randomizations=1000, return_details=False, expectation=0, n_cores=1,
+                                         ctx: Context | None = None):
+    """scde.test.gene.expression.difference (R/functions.R:783-846, 934-946; no plots): the
+    expression difference of one gene between the two levels of ``groups``, optionally corrected
+    for ``batch``.
+
+    ``gene`` names a row of ``counts`` (a DataFrame; for a bare array, its 0-based row).  Each
+    group's joint posterior comes from ``scde_posteriors`` on the group's own cells, their ratio
+    from ``calculate_ratio_posterior`` and the one-row table (lb, mle, ub, ce, Z, cZ) from
+    ``quick_distribution_summary``.  With more than one ``batch`` level the batch posteriors are
+    computed over all cells (``batch_models``, default ``models``) with each group's batch
+    composition, and the group ratio is divided by their ratio on a uniform prior
+    (``skip_prior_adjustment``).  A ``None`` in ``groups`` or ``batch`` is NA: the cell belongs to
+    no level.  The reference's printed notices about batches found in one group only are a
+    ``warnings.warn``; its Fisher test of the group-batch table, which only prints, is left out.
+
+    Returns the one-row table; with ``return_details`` {"results", "difference.posterior",
+    "posteriors": {level: {"jp", "post"}}}, or with batch correction {"results",
+    "difference.posterior", "results.nobatchcorrection"}."""
+    ctx = ctx or default_context()
+    _, genes, _ = _counts_matrix(counts)
+    if genes is not None:
+        if str(gene) not in genes:
+            raise ValueError(f"ERROR: specified gene ({gene}) is not found in the count data")
+        row = counts.iloc[[genes.index(str(gene))]]
+    else:
+        a = np.asarray(counts)
+        if isinstance(gene, (str, bytes)) or not 0 <= int(gene) < a.shape[0]:
+            raise ValueError(f"ERROR: specified gene ({gene}) is not found in the count data")
+        row = a[[int(gene)]]
+    mat, _ = _align_counts(models, row)
+    if groups is None:
+        groups = getattr(models, "attrs", {}).get("groups")
+        if groups is None:
+            raise ValueError("ERROR: groups factor is not provided, and models structure is lacking groups "
+                             "attribute")
+    codes = _groups_vector(models, groups)
+    names = _group_levels(groups)
+    md = as_model_dict(models)
+    jpl = []
+    for lv in (0, 1):
+        ii = np.nonzero(codes == lv)[0]
+        jpl.append(scde_posteriors({k: v[ii] for k, v in md.items()}, mat[:, ii], prior,
+                                   n_randomizations=n_randomizations, return_individual_posteriors=True,
+                                   n_cores=n_cores, ctx=ctx))
+    label = [str(gene)]
+    bdiffp = calculate_ratio_posterior(jpl[0]["jp"], jpl[1]["jp"], prior, n_cores=n_cores)
+    bdiffp.rownames = label
+    rep = quick_distribution_summary(bdiffp, expectation)
+    blist = None if batch is None else np.asarray(batch, dtype=object).tolist()
+    levels = sorted(set(b for b in blist if b is not None)) if blist is not None else []
+    if len(levels) <= 1:
+        if return_details:
+            return {"results": rep, "difference.posterior": bdiffp, "posteriors": dict(zip(names, jpl))}
+        return rep
+    if len(blist) != mat.shape[1]:
+        raise ValueError("batch must have one value per cell of models")
+    known = np.array([b is not None for b in blist])
+    comps = [[int(sum(1 for i in np.nonzero(codes == lv)[0] if blist[i] == b)) for b in levels] for lv in (0, 1)]
+    if any(c == 0 for comp in comps for c in comp):
+        import warnings
+        warnings.warn("ERROR: cannot control for batch effect, as some batches are found only in one group: "
+                      f"{dict(zip(names, comps))}")
+    # a cell without a batch label is in no level's list and is never drawn: leaving it out of
+    # the call changes nothing
+    bmd = as_model_dict(batch_models if batch_models is not None else models)
+    bsub = {k: v[known] for k, v in bmd.items()}
+    bkn = [b for b in blist if b is not None]
+    bjp = [scde_posteriors(bsub, mat[:, known], prior, n_randomizations=n_randomizations, batch=bkn,
+                           composition=comp, n_cores=n_cores, ctx=ctx) for comp in comps]
+    batch_bdiffp = calculate_ratio_posterior(bjp[0], bjp[1], prior, n_cores=n_cores)
+    ncol = bdiffp.values.shape[1]
+    a_bdiffp = calculate_ratio_posterior(bdiffp.values, batch_bdiffp.values,
+                                         {"x": bdiffp.columns, "y": np.full(ncol, 1.0 / ncol)},
+                                         skip_prior_adjustment=True)
+    a_bdiffp.rownames = label
+    a_rep = quick_distribution_summary(a_bdiffp, expectation)
+    if return_details:
+        return {"results": a_rep, "difference.posterior": a_bdiffp, "results.nobatchcorrection": rep}
+    return a_rep
+
+
 def bh_cz(z):
     """cZ from Z (R/functions.R:5051), computed by the library's host code."""
     return _bh(z)
@@ -508,7 +598,8 @@ def bh_cz_device(ctx: Context, z_ptr: int, n: int, cz_ptr: int):
     check(lib().scde_bh_cz_dev(ctx.handle, ctypes.c_void_p(z_ptr), int(n), ctypes.c_void_p(cz_ptr)))
 
 
-__all__ = ["scde_posteriors", "scde_expression_difference", "calculate_ratio_posterior", "quick_distribution_summary",
+__all__ = ["scde_posteriors", "scde_expression_difference", "scde_test_gene_expression_difference",
+           "calculate_ratio_posterior", "quick_distribution_summary",
            "logBootPosterior", "logBootBatchPosterior", "jpmatLogBoot", "jpmatLogBatchBoot", "matSlideMult",
            "marginals", "ratio_columns", "expectation_column", "Context", "DeviceCounts", "RatioPosterior",
            "ScdeError", "bh_cz", "bh_cz_device", "set_rand"]

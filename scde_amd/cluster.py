@@ -4,6 +4,9 @@ PAGODA steps that consume a distance matrix.
   * ``hclust`` / ``hclust_batch``          R's ``stats::hclust`` for ward.D, ward.D2, single,
                                            complete, average, mcquitty (merge, height, order in
                                            R's encoding)
+  * ``dist`` / ``hclust_dist``             R's ``stats::dist`` between the rows of a matrix
+                                           (euclidean, manhattan, maximum; csrc/rdist.hip), and
+                                           ``hclust(dist(x))`` with the matrix kept in HBM
   * ``cutree``                             R's ``cutree`` (numpy; O(n) per cut)
   * ``order_optimal`` / ``leaf_order_length``  ``cba::order.optimal``: the orientation of a tree
                                            whose leaf order has the smallest summed distance
@@ -83,6 +86,71 @@ def _hclust_dev(ctx, ptr, n, method, labels=None):
     check(lib().scde_hclust_dev(ctx.handle, ptr, n, n, _method_code(method), api._p(merge), api._p(height),
                                 api._p(order)))
     return HClust(merge, height, order, method, labels)
+
+
+DIST_METHODS = ("euclidean", "manhattan", "maximum")
+
+
+def _dist_code(method):
+    if method not in DIST_METHODS:
+        raise ValueError(f"unknown method {method!r}: one of {', '.join(DIST_METHODS)}")
+    return DIST_METHODS.index(method)
+
+
+def _dist_input(x):
+    """(Fortran-ordered float64 n x p matrix, row labels or None)."""
+    labels = [str(v) for v in x.index] if hasattr(x, "index") and hasattr(x, "columns") else None
+    a = np.asarray(x.values if labels is not None else x, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] < 1:
+        raise ValueError("x must be an n x p matrix with at least one row")
+    return np.asfortranarray(a), labels
+
+
+def dist(x, method="euclidean", ctx: api.Context | None = None):
+    """R's ``as.matrix(dist(x, method))`` (csrc/rdist.hip; the contract is in
+    include/scde_hip.h): the distances between the rows of the n x p ``x`` as the symmetric
+    n x n float64 matrix with a zero diagonal, which ``hclust`` takes as it stands.  ``method``:
+    "euclidean", "manhattan" or "maximum".  A column takes part in a pair when neither value is
+    NaN and the difference is not NaN; sums over fewer than p columns are scaled up by
+    p / count, and a pair without a common column is NaN, as in R.  A DataFrame's row labels come
+    back on a DataFrame.  Written from R's documentation and C loop; not checked against a run
+    of R."""
+    code = _dist_code(method)
+    a, labels = _dist_input(x)
+    n, p = a.shape
+    out = np.zeros((n, n), order="F")
+    check(lib().scde_dist_host(ctx.handle if ctx else None, api._p(a), n, n, p, code, api._p(out)))
+    if labels is not None:
+        import pandas as pd
+        return pd.DataFrame(out, index=labels, columns=labels)
+    return out
+
+
+def hclust_dist(x, dist_method="euclidean", method="complete", ctx: api.Context | None = None):
+    """``hclust(dist(x, dist_method), method)`` with the distance matrix formed in HBM and
+    clustered there (it never visits the host).  R's defaults for both methods."""
+    _method_code(method)
+    code = _dist_code(dist_method)
+    ctx = ctx or api.default_context()
+    a, labels = _dist_input(x)
+    n, p = a.shape
+    if n < 2:
+        raise ValueError("at least 2 objects are needed")
+    L = lib()
+    bufs = []
+    try:
+        for nbytes in (max(a.nbytes, 8), 8 * n * n):
+            ptr = ctypes.c_void_p()
+            check(L.scde_dev_alloc(ctx.handle, nbytes, ctypes.byref(ptr)))
+            bufs.append(ptr)
+        xd, dd = bufs
+        if a.nbytes:
+            check(L.scde_h2d(ctx.handle, xd, api._p(a), a.nbytes))
+        check(L.scde_dist_dev(ctx.handle, xd, n, n, p, code, dd))
+        return _hclust_dev(ctx, dd, n, method, labels)
+    finally:
+        for ptr in bufs:
+            L.scde_dev_free(ctx.handle, ptr)
 
 
 def hclust_batch(ds, method="ward.D", ctx: api.Context | None = None):

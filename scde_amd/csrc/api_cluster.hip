@@ -1,7 +1,7 @@
-// api_cluster.hip -- the host side of dist.hip, hclust.hip, olo.hip, tsne.hip, knn.hip, knn_fit.hip,
-// error_models.hip and nb2_fit.hip: the cell-to-cell distance measures, hierarchical clustering,
-// optimal leaf ordering, exact t-SNE, and the error-model fitters (knn.error.models,
-// scde.error.models).  (engine.hip is
+// api_cluster.hip -- the host side of dist.hip, rdist.hip, hclust.hip, olo.hip, tsne.hip, knn.hip,
+// knn_fit.hip, error_models.hip and nb2_fit.hip: the cell-to-cell distance measures, stats::dist,
+// hierarchical clustering, optimal leaf ordering, exact t-SNE, and the error-model fitters
+// (knn.error.models, scde.error.models).  (engine.hip is
 // the pipeline; a feature's host code lives in the api_ file named after its kernel files.)
 #include <algorithm>
 #include <cmath>
@@ -181,6 +181,52 @@ int scde_direct_corr_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngen
   RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
   return scde_direct_corr_dev(ctx, dev, ngenes, ngenes, ncells, models, square_logit_conc, k, nsim, uniforms, seed,
                               out);
+}
+
+// ------------------------------------------------------------------ stats::dist
+// R's dist between the rows of an n x p matrix (rdist.hip; contract in scde_hip.h).  Arguments
+// are checked before the GPU is touched.
+static int rdist_check(const void* x, int64_t ld, int n, int p, int method, const void* out) {
+  if (!x || !out) return fail(SCDE_EARG, "null argument");
+  if (n < 1 || p < 0) return fail(SCDE_EARG, "dist: n must be at least 1 and p at least 0");
+  if (ld < n) return fail(SCDE_EARG, "dist: ld must be at least n");
+  if (method < 0 || method > 2)
+    return fail(SCDE_EARG, "dist: unknown method code %d (0 euclidean, 1 manhattan, 2 maximum)", method);
+  if (n > (1 << 21)) return fail(SCDE_EARG, "dist: more than %d objects", 1 << 21);
+  return SCDE_OK;
+}
+
+int scde_dist_dev(scde_ctx* ctx, const double* x_dev, int64_t ld, int n, int p, int method, double* out_dev) {
+  FORK_GUARD();
+  RCHK(rdist_check(x_dev, ld, n, p, method, out_dev));
+  RCHK(use_ctx(ctx));
+  HCHK(ctx->rd_flag.ensure(sizeof(int)));
+  HCHK(launch_rdist_flag(x_dev, ld, n, p, ctx->rd_flag.as<int>(), ctx->stream));
+  int flag = 0;
+  HCHK(hipMemcpyAsync(&flag, ctx->rd_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_rdist(x_dev, ld, n, p, method, flag != 0, out_dev, ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  return ctx->sync();
+}
+
+int scde_dist_host(scde_ctx* ctx, const double* x, int64_t ld, int n, int p, int method, double* out) {
+  FORK_GUARD();
+  RCHK(rdist_check(x, ld, n, p, method, out));
+  RCHK(use_ctx(ctx));
+  const size_t ob = sizeof(double) * (size_t)n * n;
+  if (ctx->hc_in.ensure(ob) != hipSuccess)
+    return fail_oom("dist: out of memory: the result needs %zu bytes of device memory", ob);
+  RCHK(put_matrix(ctx, ctx->rd_x, x, ld, n, p));
+  int rc = scde_dist_dev(ctx, ctx->rd_x.as<double>(), n, n, p, method, ctx->hc_in.as<double>());
+  if (rc == SCDE_OK) {
+    hipError_t e = hipMemcpyAsync(out, ctx->hc_in.p, ob, hipMemcpyDeviceToHost, ctx->stream);
+    rc = e != hipSuccess ? fail(SCDE_EHIP, "dist: %s", hipGetErrorString(e)) : ctx->sync();
+  }
+  if (sizeof(double) * (size_t)n * p > ((size_t)1 << 30)) ctx->rd_x.release();
+  if (ob > ((size_t)1 << 30)) ctx->hc_in.release();
+  return rc;
 }
 
 // ------------------------------------------------------------------ hierarchical clustering

@@ -237,6 +237,9 @@ struct scde_ctx {
   // hierarchical clustering (hclust.hip): a host matrix staged, the problems' workspaces, the
   // problem descriptors, the raw steps (oi, oj, oh, flags)
   Buf hc_in, hc_ws, hc_prob, hc_out;
+  // stats::dist (rdist.hip): a host matrix staged, the non-finite flag (a host call's result is
+  // staged in hc_in)
+  Buf rd_x, rd_flag;
   // the random rounds of pagoda.gene.clusters: raw twister words, keep flags / column lists,
   // sigma1's problem lists, workspace and results
   Buf gr_raw, gr_int, gr_prob, gr_ws, gr_out;

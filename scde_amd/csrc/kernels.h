@@ -490,6 +490,15 @@ int olo_check_merge(int n, const int* merge, char* msg, size_t cap);
 int olo_solve(hipStream_t s, const double* d_dev, long long ld, int n, const int* merge, int* merge_out,
               int* order_out, double* length, double* stats, char* msg, size_t cap);
 
+// ---- stats::dist between the rows of a resident column-major n x p matrix (rdist.hip; the
+// contract is in include/scde_hip.h).
+// *flag = 1 when any value of x is NaN or infinite, otherwise 0
+hipError_t launch_rdist_flag(const double* x, long long ld, int n, int p, int* flag, hipStream_t s);
+// method 0 euclidean, 1 manhattan, 2 maximum; count = false only for an x without NaN or Inf;
+// out: n x n, both triangles, the diagonal 0; n such that the lower-triangle 64 x 64 tiles fit a grid
+hipError_t launch_rdist(const double* x, long long ld, int n, int p, int method, bool count, double* out,
+                        hipStream_t s);
+
 // ---- exact t-SNE of a distance matrix (tsne.hip; the contract is in include/scde_hip.h).
 struct TsneParams {
   double eta, exaggeration, momentum, final_momentum;
