@@ -945,6 +945,51 @@ int scde_knn_magnitudes_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, in
 int scde_knn_magnitudes_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const int* nb,
                              int kmax, const double* ls, int thr, double trim, double* fpm, int* nabove);
 
+/* ---------------------------------------------------------------- Spearman rank correlation
+ * (csrc/spearman.hip, driven by scde_amd/spearman.py and scde_amd/cluster.py)
+ *
+ * Rank transform.  x is nrow x ncol column-major (a column contiguous); every column of out
+ * receives R's rank(column, ties.method = "average", na.last = "keep"): a value's rank is the
+ * number of smaller values of its column plus (the number equal to it, itself included, + 1) / 2.
+ * Values are FP64; -0.0 and 0.0 tie; a NaN stays the NaN it is and the other values are ranked
+ * among the non-NaN ones; +-Inf are ordinary values.  Every rank is a multiple of 0.5 and exact.
+ * out may be x (in place).  Columns of up to 8192 rows are sorted in LDS, one workgroup per
+ * column; longer ones are ranked by counting, O(nrow^2) per column (in place, that path takes a
+ * second nrow x ncol matrix of device memory).  No atomics: results are the same every run and
+ * the two entries agree bit for bit.  nrow, ncol >= 1.  ctx may be NULL. */
+int scde_rank_cols_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev);
+int scde_rank_cols_host(scde_ctx* ctx, const double* x, int nrow, int ncol, double* out);
+/* Pairwise-complete Spearman similarity of cells: what knn.error.models(cor.method = "spearman")
+ * computes (R/functions.R:1184-1196), stats::cor(method = "spearman", use = "pairwise.complete.obs")
+ * of sqrt(counts) with the entries below thr set to NA.  Arguments, layout and limits are those of
+ * scde_knn_similarity_*: counts int32, ngenes x ncells column-major with leading dimension ld,
+ * valid where counts[g, c] >= thr; out is ncells x ncells (host); at most 8192 cells; and at most
+ * 1,300,000 genes, which keeps every sum below exact in int64.  The host entry refuses a negative
+ * count (SCDE_EARG); in resident counts a negative entry is never valid.  ctx may be NULL.
+ *
+ * For cells i and j (i = j included), with S = { g : counts[g, i] >= thr and counts[g, j] >= thr }
+ * and m = |S| (sqrt is monotone, so the counts are ranked):
+ *   a_g = 2 #{h in S : c_hi < c_gi} + #{h in S : c_hi = c_gi} + 1     twice g's average rank in cell i
+ *   b_g = the same in cell j
+ *   sum a = sum b = m (m + 1), so with M = m (m + 1)^2
+ *   Sab = sum a_g b_g - M,  Saa = sum a_g^2 - M,  Sbb = sum b_g^2 - M   exact int64 integers
+ *   out[i, j] = (double)Sab / sqrt((double)Saa * (double)Sbb), clamped to [-1, 1]
+ * three correctly rounded operations on exact integers (no fused multiply-add), so the result does
+ * not depend on any order of summation.  NaN when m = 0, Saa = 0 or Sbb = 0 (m = 1; a cell whose
+ * common genes all tie).  The diagonal goes through the same formula: 1.0, or NaN for a cell with
+ * no valid gene or a single valid value.  The matrix is symmetric bit for bit.  R sums the same
+ * ranks in long double in two passes; the two agree to rounding, not bit for bit.
+ *
+ * lds_values: a pair whose two rank tables (one entry per distinct valid value of either cell)
+ * have more entries than this keeps them in a global workspace instead of LDS; 0 is the kernel's
+ * maximum (36864).  Both paths give the same bits; a small value is the test hook for the
+ * workspace path.  The matrix also stays resident in the context for scde_knn_neighbours
+ * (sim = NULL), as scde_knn_similarity_* leave theirs. */
+int scde_spearman_similarity_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, int thr,
+                                 int lds_values, double* out);
+int scde_spearman_similarity_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, int thr,
+                                  int lds_values, double* out);
+
 /* ---------------------------------------------------------------- knn.error.models, mixture fit
  * One two-component EM per cell (fit.nb2gth.mixture.model and get.compressed.v1.model,
  * R/functions.R:3653-3660, 4058-4187, 3422-3434; csrc/knn_fit.hip; the contract, step by step, is

@@ -22,6 +22,7 @@ from .knn import (estimate_library_sizes, knn_cell_data, knn_cell_similarity, kn
                   knn_expected_magnitudes, knn_fit_models, knn_model_inputs, knn_neighbours, tmm_norm_factors)
 from .prep import clean_counts, clean_gos  # noqa: F401
 from .prior import expression_prior  # noqa: F401
+from .spearman import rank_columns, spearman_cell_similarity  # noqa: F401
 from .top_aspects import pagoda_effective_cells, pagoda_top_aspects, top_aspects_table  # noqa: F401
 from .views import pagoda_show_pathways, pagoda_view_aspects, view_pathway_genes  # noqa: F401
 from .varnorm import (EdfTable, fit_trend, load_edf_table, pagoda_subtract_aspect, pagoda_varnorm)  # noqa: F401

@@ -44,6 +44,7 @@ EXPORTS = [
     "scde_knn_magnitudes_dev", "scde_knn_magnitudes_host", "scde_knn_fit_dev", "scde_knn_fit_host",
     "scde_crossfit_inputs_dev", "scde_crossfit_inputs_host", "scde_nb2_fit_dev", "scde_nb2_fit_host",
     "scde_dist_host", "scde_dist_dev",
+    "scde_rank_cols_dev", "scde_rank_cols_host", "scde_spearman_similarity_dev", "scde_spearman_similarity_host",
 ]
 
 
@@ -187,6 +188,9 @@ def lib():
         L.scde_nb2_fit_dev.argtypes = L.scde_nb2_fit_host.argtypes = [P, P, i64, i, i, P, P, d, i, i, P, P, P, P, P, P]
     if hasattr(L, "scde_dist_dev"):  # (likewise: a build from before stats::dist)
         L.scde_dist_host.argtypes = L.scde_dist_dev.argtypes = [P, P, i64, i, i, i, P]
+    if hasattr(L, "scde_rank_cols_dev"):  # (likewise: a build from before Spearman)
+        L.scde_rank_cols_dev.argtypes = L.scde_rank_cols_host.argtypes = [P, P, i, i, P]
+        L.scde_spearman_similarity_dev.argtypes = L.scde_spearman_similarity_host.argtypes = [P, P, i64, i, i, i, i, P]
     _lib = L
     return L
 

@@ -325,10 +325,11 @@ def pagoda_cluster_cells(tam, varinfo, method="ward.D", include_aspects=False, r
 
 def pagoda_gene_clusters_observed(varinfo, trim=None, n_clusters=150, n_starts=10, n_components=1,
                                   n_internal_shuffles=0, method="ward.D", secondary_correlation=False, seed=1,
-                                  return_details=False, ctx: api.Context | None = None):
+                                  return_details=False, cor_method="pearson", ctx: api.Context | None = None):
     """The observed half of ``pagoda.gene.clusters`` (R/functions.R:2060-2121): winsorize
     (``trim`` defaults to 3.1 / ncells), centre by batch, drop constant rows, cluster the genes
-    on 1 - cor (Pearson; optionally the correlation of that distance matrix again), cut into
+    on 1 - cor (``cor_method`` "pearson" / "p", or "spearman": the genes ranked over the cells on
+    the device first; optionally the Pearson correlation of that distance matrix again), cut into
     ``n_clusters`` and run one ``bwpca`` per cluster, oriented as R/functions.R:2114-2117.
 
     The gene x gene distance is formed in HBM and clustered there.  Returns {"clusters":
@@ -339,7 +340,9 @@ def pagoda_gene_clusters_observed(varinfo, trim=None, n_clusters=150, n_starts=1
     ``seed`` + its 0-based position."""
     from .pagoda import (DeviceMatrixPair, RState, WpcaBatch, _r_cor, shuffle_perms, weighted_mat_center,
                          winsorize_matrix)
+    from .spearman import cor_method_is_spearman
     _method_code(method)
+    spearman = cor_method_is_spearman(cor_method)
     ctx = ctx or api.default_context()
     mat = np.asarray(varinfo["mat"], dtype=np.float64)
     matw = np.asarray(varinfo["matw"], dtype=np.float64)
@@ -371,6 +374,8 @@ def pagoda_gene_clusters_observed(varinfo, trim=None, n_clusters=150, n_starts=1
         xd = dev(x.nbytes)
         check(L.scde_h2d(ctx.handle, xd, api._p(x), x.nbytes))
         gd = dev(8 * ng * ng)
+        if spearman:  # (only the distance sees the ranks: xd is not used again)
+            check(L.scde_rank_cols_dev(ctx.handle, xd, ncells, ng, xd))
         check(L.scde_cor_distance_dev(ctx.handle, xd, ncells, ng, gd))
         if secondary_correlation:
             gd2 = dev(8 * ng * ng)
@@ -453,11 +458,13 @@ def _hclust_ws_bytes(n):
 
 def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples=60, method="ward.D",
                                 secondary_correlation=False, rounds_per_batch=None, matrices=None,
-                                return_details=False, timings=None, ctx: api.Context | None = None):
+                                return_details=False, timings=None, cor_method="pearson",
+                                ctx: api.Context | None = None):
     """The randomised half of ``pagoda.gene.clusters`` (R/functions.R:2131-2192), n.cores = 1:
     for round i = 1..n_samples, ``set.seed(i)``, ``matrix(rnorm(ngenes * n_cells), nrow = ngenes)``,
     winsorize (``trim`` > 0), keep the genes with ``abs(sum(diff(abs(x)))) > 0``, cluster them on
-    1 - cor (optionally the correlation of that distance again), cut into ``n_clusters`` and take
+    1 - cor (``cor_method`` "pearson" / "p", or "spearman": the kept genes ranked over the cells;
+    optionally the Pearson correlation of that distance again), cut into ``n_clusters`` and take
     per cluster ``pcaMethods::sDev(pca(m[, ii], nPcs = 1, center = FALSE))^2``, read as
     sigma_1^2 / max(1, n_cells - 1) (from memory of pcaMethods; not checked against it).
 
@@ -483,7 +490,9 @@ def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples
     "clustering", "sigma1"."""
     import time
     from concurrent.futures import ThreadPoolExecutor
+    from .spearman import cor_method_is_spearman
     code = _method_code(method)
+    spearman = cor_method_is_spearman(cor_method)
     ngenes, n_cells, n_clusters = int(ngenes), int(n_cells), int(n_clusters)
     if matrices is not None:
         matrices = [np.ascontiguousarray(m, dtype=np.float64) for m in matrices]
@@ -509,7 +518,8 @@ def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples
         free, _ = dev_mem_info(ctx)
         per_round = (dsz * (2 if secondary_correlation else 1) + _hclust_ws_bytes(ngenes) + 16 * ngenes + msz
                      + 8 * (ngenes + 4) * min(ngenes, n_cells) + 256)
-        rounds_per_batch = (free // 2 - 3 * msz) // per_round  # raw, wz and the library's word buffer
+        # raw, wz and the library's word buffer (and the ranks, and the counting path's copy of them)
+        rounds_per_batch = (free // 2 - (5 if spearman else 3) * msz) // per_round
     B = int(max(1, min(int(rounds_per_batch), n_samples)))
     tm = timings if timings is not None else {}
     for k in ("draw", "winsorize", "distance", "clustering", "sigma1"):
@@ -538,6 +548,8 @@ def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples
         xw = dev(B * msz)       # the batch's winsorized, kept matrices: n_cells x (B * ngenes)
         gd = dev(B * dsz)       # the batch's distance matrices, round r at element r * ngenes^2
         gd2 = dev(B * dsz) if secondary_correlation else None
+        # the ranks of a round's kept genes: only the distance sees them, sigma1 takes the values in xw
+        rk = dev(msz) if spearman else None
         for b0 in range(0, n_samples, B):
             nb = min(B, n_samples - b0)
             nk = np.zeros(nb, np.int32)
@@ -569,7 +581,9 @@ def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples
                 nk[r] = len(vi)
                 t0 = timed("winsorize", t0)
                 dr = _ptr(gd, r * dsz)
-                check(L.scde_cor_distance_dev(ctx.handle, slot, n_cells, int(nk[r]), dr))
+                if spearman:
+                    check(L.scde_rank_cols_dev(ctx.handle, slot, n_cells, int(nk[r]), rk))
+                check(L.scde_cor_distance_dev(ctx.handle, rk if spearman else slot, n_cells, int(nk[r]), dr))
                 if secondary_correlation:
                     check(L.scde_cor_distance_dev(ctx.handle, dr, int(nk[r]), int(nk[r]), _ptr(gd2, r * dsz)))
                 timed("distance", t0)
@@ -630,7 +644,7 @@ def pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=150, n_samples
 
 def pagoda_gene_clusters(varinfo, trim=None, n_clusters=150, n_samples=60, n_internal_shuffles=0, n_starts=10,
                          n_components=1, method="ward.D", secondary_correlation=False, n_cells=None, old_results=None,
-                         seed=1, ctx: api.Context | None = None):
+                         seed=1, cor_method="pearson", ctx: api.Context | None = None):
     """``pagoda.gene.clusters`` (R/functions.R:2058-2237; n.cores = 1, no plot, no ``show.random``):
     the observed clusters (``pagoda_gene_clusters_observed``) scored against the null model of
     ``pagoda_gene_cluster_samples`` on ``nrow(varinfo$mat)`` x ``n_cells`` random matrices
@@ -643,9 +657,12 @@ def pagoda_gene_clusters(varinfo, trim=None, n_clusters=150, n_samples=60, n_int
     likelihood fit of ``varst`` {"location", "scale"} (``scde_amd.rmt``).
 
     ``old_results`` reuses its "clusters" / "cl.goc" and, when it has one, its "varm" (n, var,
-    round), as R/functions.R:2074-2129 do; with a "varm" no device work is done."""
+    round), as R/functions.R:2074-2129 do; with a "varm" no device work is done.  ``cor_method``
+    ("pearson", "p" or "spearman") is the correlation of both halves' gene distance."""
     from . import rmt
+    from .spearman import cor_method_is_spearman
     _method_code(method)
+    cor_method_is_spearman(cor_method)
     ngenes, ncol = np.asarray(varinfo["mat"]).shape
     if trim is None:
         trim = 3.1 / ncol
@@ -656,13 +673,14 @@ def pagoda_gene_clusters(varinfo, trim=None, n_clusters=150, n_samples=60, n_int
         obs = pagoda_gene_clusters_observed(varinfo, trim=trim, n_clusters=n_clusters, n_starts=n_starts,
                                             n_components=n_components, n_internal_shuffles=n_internal_shuffles,
                                             method=method, secondary_correlation=secondary_correlation, seed=seed,
-                                            ctx=ctx)
+                                            cor_method=cor_method, ctx=ctx)
         clusters, goc = obs["clusters"], obs["cl.goc"]
     if old_results is not None and old_results.get("varm") is not None:
         varm = {k: np.asarray(old_results["varm"][k]) for k in ("n", "var", "round")}
     else:
         varm = pagoda_gene_cluster_samples(ngenes, n_cells, trim, n_clusters=n_clusters, n_samples=n_samples,
-                                           method=method, secondary_correlation=secondary_correlation, ctx=ctx)
+                                           method=method, secondary_correlation=secondary_correlation,
+                                           cor_method=cor_method, ctx=ctx)
     varm, clvlm, tci = rmt.score_varm(varm, n_cells)
     xf = rmt.gumbel_fit(varm["varst"])
     return {"clusters": clusters, "xf": xf, "tci": tci, "cl.goc": goc, "varm": varm, "clvlm": clvlm, "trim": trim}

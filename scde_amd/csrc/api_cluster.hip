@@ -598,6 +598,98 @@ int scde_knn_similarity_host(scde_ctx* ctx, const int* counts, int64_t ld, int n
   return scde_knn_similarity_dev(ctx, dev, ngenes, ngenes, ncells, thr, out);
 }
 
+// ------------------------------------------------------------------ Spearman (spearman.hip)
+int scde_rank_cols_dev(scde_ctx* ctx, const double* x_dev, int nrow, int ncol, double* out_dev) {
+  FORK_GUARD();
+  if (!x_dev || !out_dev) return fail(SCDE_EARG, "rank_cols: null argument");
+  if (nrow < 1 || ncol < 1) return fail(SCDE_EARG, "rank_cols: bad dimensions (nrow = %d, ncol = %d)", nrow, ncol);
+  RCHK(use_ctx(ctx));
+  double* tmp = nullptr;
+  if (x_dev == out_dev && rank_cols_needs_tmp(nrow)) {
+    const size_t nb = sizeof(double) * (size_t)nrow * ncol;
+    if (ctx->sp_tmp.ensure(nb) != hipSuccess)
+      return fail_oom("rank_cols: out of memory: ranking %d rows in place needs %zu bytes of device memory", nrow, nb);
+    tmp = ctx->sp_tmp.as<double>();
+  }
+  HCHK(launch_rank_cols(x_dev, nrow, ncol, out_dev, tmp, ctx->stream));
+  return ctx->sync();
+}
+
+int scde_rank_cols_host(scde_ctx* ctx, const double* x, int nrow, int ncol, double* out) {
+  FORK_GUARD();
+  if (!x || !out) return fail(SCDE_EARG, "rank_cols: null argument");
+  if (nrow < 1 || ncol < 1) return fail(SCDE_EARG, "rank_cols: bad dimensions (nrow = %d, ncol = %d)", nrow, ncol);
+  RCHK(use_ctx(ctx));
+  const size_t nb = sizeof(double) * (size_t)nrow * ncol;
+  if (ctx->sp_x.ensure(nb) != hipSuccess || (rank_cols_needs_tmp(nrow) && ctx->sp_tmp.ensure(nb) != hipSuccess))
+    return fail_oom("rank_cols: out of memory: a %d x %d matrix needs %zu bytes of device memory", nrow, ncol, nb);
+  HCHK(hipMemcpyAsync(ctx->sp_x.p, x, nb, hipMemcpyHostToDevice, ctx->stream));
+  HCHK(launch_rank_cols(ctx->sp_x.as<double>(), nrow, ncol, ctx->sp_x.as<double>(), ctx->sp_tmp.as<double>(),
+                        ctx->stream));
+  HCHK(hipMemcpyAsync(out, ctx->sp_x.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+  return ctx->sync();
+}
+
+// 4 m^3 < 2^63 keeps the centred sums exact in int64
+static constexpr int kSpearmanMaxGenes = 1300000;
+
+int scde_spearman_similarity_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, int thr,
+                                 int lds_values, double* out) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "spearman_similarity"));
+  if (!out) return fail(SCDE_EARG, "spearman_similarity: null argument");
+  if (ngenes > kSpearmanMaxGenes)
+    return fail(SCDE_EARG, "spearman_similarity: %d genes, at most %d are supported", ngenes, kSpearmanMaxGenes);
+  if (lds_values < 0) return fail(SCDE_EARG, "spearman_similarity: lds_values must not be negative");
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells;
+  const size_t cb = std::max<size_t>(1, (size_t)spearman_code_bytes(N) * spearman_code_ld(N) * C), cc = sizeof(double) * (size_t)C * C;
+  const size_t w1 = spearman_codes_ws_bytes(N, C);
+  ctx->kn_sim_c = -1;
+  if (ctx->sp_codes.ensure(cb) != hipSuccess || ctx->sp_d.ensure(sizeof(int) * (size_t)C) != hipSuccess ||
+      ctx->kn_sim.ensure(cc) != hipSuccess || (w1 && ctx->sp_ws.ensure(w1) != hipSuccess))
+    return fail_oom("spearman_similarity: out of memory: the codes of %d x %d counts, a %d x %d matrix and the "
+                    "workspace need %zu bytes",
+                    N, C, C, C, cb + cc + w1);
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_spearman_codes(counts_dev, ld, N, C, thr, ctx->sp_codes.p, ctx->sp_d.as<int>(),
+                             w1 ? ctx->sp_ws.as<unsigned>() : nullptr, ctx->stream));
+  // the tables are sized from the largest number of distinct values the prepass found
+  std::vector<int> D((size_t)C);
+  HCHK(hipMemcpyAsync(D.data(), ctx->sp_d.p, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  int dmax = 0;
+  for (int c = 0; c < C; ++c) {
+    if (D[c] < 0 || D[c] > N) return fail(SCDE_EHIP, "spearman_similarity: cell %d has %d distinct values", c, D[c]);
+    dmax = std::max(dmax, D[c]);
+  }
+  const size_t w2 = spearman_pairs_ws_bytes(C, dmax, lds_values);
+  if (w2 && ctx->sp_ws.ensure(w2) != hipSuccess)
+    return fail_oom("spearman_similarity: out of memory: the tables of the pairs too large for LDS need %zu bytes",
+                    w2);
+  HCHK(launch_spearman_pairs(ctx->sp_codes.p, N, C, ctx->sp_d.as<int>(), dmax, lds_values,
+                             w2 ? ctx->sp_ws.as<unsigned>() : nullptr, ctx->kn_sim.as<double>(), ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  HCHK(hipMemcpyAsync(out, ctx->kn_sim.p, cc, hipMemcpyDeviceToHost, ctx->stream));
+  RCHK(ctx->sync());
+  ctx->kn_sim_c = C;
+  return SCDE_OK;
+}
+
+int scde_spearman_similarity_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, int thr,
+                                  int lds_values, double* out) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "spearman_similarity"));
+  if (!out) return fail(SCDE_EARG, "spearman_similarity: null argument");
+  for (int c = 0; c < ncells; ++c)
+    for (int g = 0; g < ngenes; ++g)
+      if (counts[(size_t)c * ld + g] < 0)
+        return fail(SCDE_EARG, "spearman_similarity: count (%d, %d) is negative", g, c);
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_spearman_similarity_dev(ctx, dev, ngenes, ngenes, ncells, thr, lds_values, out);
+}
+
 int scde_knn_neighbours(scde_ctx* ctx, const double* sim, int ncells, const int* groups, int k, int kmax, int* out) {
   FORK_GUARD();
   const int C = ncells;

@@ -258,6 +258,9 @@ struct scde_ctx {
   // before they go to the host
   Buf kn_sim, kn_nb, kn_int, kn_ls, kn_fpm, kn_nab;
   int kn_sim_c = -1, kn_nb_c = -1, kn_nb_k = -1;
+  // Spearman (spearman.hip): a host matrix staged for the rank transform and the counting path's
+  // second copy; the similarity's dense codes, distinct-value counts and workspace
+  Buf sp_x, sp_tmp, sp_codes, sp_d, sp_ws;
   // knn.error.models' mixture fit: fpm and the starting posteriors staged, the workspace of the
   // cells too large for LDS, the results before they go to the host
   Buf kf_fpm, kf_fp, kf_ws, kf_models, kf_int, kf_llh, kf_cl, kf_post;

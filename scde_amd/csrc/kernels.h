@@ -627,4 +627,27 @@ hipError_t launch_nb2_fit(const int* counts, long long ld, int N, int C, const d
 hipError_t launch_top_aspects(const double* x, const double* w, const double* num, int m, int C, double* xv,
                               double* xvw, hipStream_t s);
 
+// ---- Spearman rank correlation (spearman.hip; contract in include/scde_hip.h).
+// launch_rank_cols: x, out nrow x ncol column-major, out == x allowed; tmp (nrow x ncol doubles) is
+// needed only when rank_cols_needs_tmp(nrow) and out == x.
+bool rank_cols_needs_tmp(int nrow);
+hipError_t launch_rank_cols(const double* x, int nrow, int ncol, double* out, double* tmp, hipStream_t s);
+// The cell similarity.  counts N x C column-major (ld); codes spearman_code_ld(N) x C,
+// spearman_code_bytes(N) bytes an entry, 16-byte aligned; D: every cell's number of distinct valid values (all codes of cell c are below
+// D[c], or the code type's largest value where the entry is not valid).  The prepass sorts in
+// LDS, or in ws (spearman_codes_ws_bytes(N, C) bytes, 0: not needed).  The pair kernel takes dmax,
+// the largest D (read back by the caller), and keeps the tables of a pair with
+// D[i] + D[j] <= min(lds_values, spearman_lds_values_max()) entries (lds_values 0: the maximum) in
+// LDS, those of a larger pair in ws (spearman_pairs_ws_bytes(C, dmax, lds_values) bytes, 0: none
+// is larger).  out: C x C column-major.
+int spearman_code_bytes(int N);
+int spearman_code_ld(int N);
+int spearman_lds_values_max();
+size_t spearman_codes_ws_bytes(int N, int C);
+size_t spearman_pairs_ws_bytes(int C, int dmax, int lds_values);
+hipError_t launch_spearman_codes(const int* counts, long long ld, int N, int C, int thr, void* codes, int* D,
+                                 unsigned* ws, hipStream_t s);
+hipError_t launch_spearman_pairs(const void* codes, int N, int C, const int* D, int dmax, int lds_values, unsigned* ws,
+                                 double* out, hipStream_t s);
+
 }  // namespace scde

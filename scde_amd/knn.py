@@ -193,7 +193,8 @@ def knn_cell_similarity(counts, thr=1, cor_method="pearson", ctx: api.Context | 
     negative: host matrices are checked, resident counts are the caller's word (a negative valid
     count, possible with ``thr <= 0``, is sqrt's NaN in every pair of its cell, as in R)."""
     if cor_method != "pearson":
-        raise NotImplementedError("only cor_method = 'pearson' is built")
+        raise NotImplementedError("only cor_method = 'pearson' is built here: the Spearman similarity is "
+                                  "spearman.spearman_cell_similarity")
     thr = _thr(thr)
     dc, mat, N, C = _counts_arg(counts)
     out = np.zeros((C, C), order="F")
@@ -314,7 +315,7 @@ def fail_priors(counts, fpm, vi, thr=1):
 
 
 def knn_model_inputs(counts, groups=None, k=None, min_nonfailed=5, min_count_threshold=1, min_size_entries=2000,
-                     min_fpm=0, fpm_estimate_trim=0.25, library_sizes=None, cor_method="pearson",
+                     min_fpm=0, fpm_estimate_trim=0.25, library_sizes=None, cor_method="pearson", similarity=None,
                      ctx: api.Context | None = None):
     """Everything ``knn.error.models`` computes before it fits a cell's mixture model.  The counts
     go to the device once; the similarity and the neighbour lists stay there between the stages.
@@ -324,11 +325,23 @@ def knn_model_inputs(counts, groups=None, k=None, min_nonfailed=5, min_count_thr
     (genes x cells bool: ``nabove >= min_nonfailed and fpm > min_fpm``; R's
     ``min(ncol(oc) - 1, min.nonfailed)`` is always min.nonfailed, as ``oc`` is a vector) and
     ``fail_prior`` (genes x cells, NaN outside ``vi``).  A cell with fewer than 40 valid genes
-    gives a warning, as R's message."""
+    gives a warning, as R's message.
+
+    ``similarity`` (cells x cells) takes the place of the Pearson similarity: the neighbours are
+    found in the caller's matrix, which need not be symmetric, and everything after them is
+    unchanged.  ``spearman.spearman_cell_similarity(counts, thr)`` is R's ``cor.method =
+    "spearman"``; ``cor_method="spearman"`` itself still raises."""
+    if similarity is not None and cor_method != "pearson":
+        raise ValueError("similarity= replaces the correlation: cor_method must be left at its default with it")
     if cor_method != "pearson":
-        raise NotImplementedError("only cor_method = 'pearson' is built")
+        raise NotImplementedError("only cor_method = 'pearson' is built here: pass similarity = "
+                                  "spearman.spearman_cell_similarity(counts, thr) for the Spearman neighbours")
     thr = _thr(min_count_threshold)
     dc, mat, N, C = _counts_arg(counts)
+    if similarity is not None:
+        similarity = np.array(similarity, dtype=np.float64, order="F")
+        if similarity.shape != (C, C):
+            raise ValueError(f"similarity must be a {C} x {C} matrix (cells x cells)")
     codes = _group_codes(groups, C)
     _handle(dc, ctx)
     host = mat if mat is not None else _host_counts(_fetch_counts(dc))  # (int32: library sizes, priors)
@@ -339,9 +352,12 @@ def knn_model_inputs(counts, groups=None, k=None, min_nonfailed=5, min_count_thr
         own = dc = api.DeviceCounts(ctx or api.default_context(), mat)
     h = dc.ctx.handle
     try:
-        sim = np.zeros((C, C), order="F")
-        check(lib().scde_knn_similarity_dev(h, dc.ptr, N, N, C, thr, api._p(sim)))
-        nb = _neighbours(None, C, k, codes, h)
+        if similarity is None:
+            sim = np.zeros((C, C), order="F")
+            check(lib().scde_knn_similarity_dev(h, dc.ptr, N, N, C, thr, api._p(sim)))
+        else:
+            sim = similarity
+        nb = _neighbours(None if similarity is None else sim, C, k, codes, h)
         fpm, nabove = _magnitudes(dc, None, N, C, None, nb.shape[1], ls, thr, trim, h)
     finally:
         if own is not None:
@@ -421,7 +437,7 @@ def knn_fit_models(inputs, counts, local_theta_fit=None, theta_fit_range=(1e-2, 
 def knn_error_models(counts, groups=None, k=None, min_nonfailed=5, min_count_threshold=1, min_size_entries=2000,
                      min_fpm=0, cor_method="pearson", fpm_estimate_trim=0.25, linear_fit=True, local_theta_fit=None,
                      theta_fit_range=(1e-2, 1e2), alpha_weight_power=0.5, iter=50, return_details=False,
-                     ctx: api.Context | None = None):
+                     similarity=None, ctx: api.Context | None = None):
     """``knn.error.models`` (R/functions.R:1158-1299): the neighbourhood stage, then every cell's
     mixture fit, both on the GPU.  Returns R's ``jmm``: a DataFrame of the cells' models, columns in
     ``models.MODEL_COLUMNS``' order (without the ``corr.ltheta.*`` columns when
@@ -429,7 +445,8 @@ def knn_error_models(counts, groups=None, k=None, min_nonfailed=5, min_count_thr
     positions) and ordered by group as R's ``rbind`` over the groups, ``.attrs["groups"]`` the rows'
     groups.  A cell whose fit fails is dropped with a warning, as R drops a ``try-error``.  With
     ``return_details``: ``(jmm, details)``, the details of ``knn_fit_models`` (all cells, in the
-    counts' order) and the model inputs under ``"inputs"``."""
+    counts' order) and the model inputs under ``"inputs"``.  ``similarity`` is
+    ``knn_model_inputs``'."""
     import pandas as pd
 
     from .models import MODEL_COLUMNS
@@ -440,7 +457,8 @@ def knn_error_models(counts, groups=None, k=None, min_nonfailed=5, min_count_thr
     cells = None if isinstance(counts, api.DeviceCounts) else api._counts_matrix(counts)[2]
     inputs = knn_model_inputs(counts, groups=groups, k=k, min_nonfailed=min_nonfailed,
                               min_count_threshold=min_count_threshold, min_size_entries=min_size_entries,
-                              min_fpm=min_fpm, fpm_estimate_trim=fpm_estimate_trim, cor_method=cor_method, ctx=ctx)
+                              min_fpm=min_fpm, fpm_estimate_trim=fpm_estimate_trim, cor_method=cor_method,
+                              similarity=similarity, ctx=ctx)
     dc = counts if isinstance(counts, api.DeviceCounts) else None
     host = counts if dc is not None else _host_counts(counts)
     mm, det = knn_fit_models(inputs, host, local_theta_fit=local, theta_fit_range=theta_fit_range,
