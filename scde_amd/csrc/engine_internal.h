@@ -680,6 +680,26 @@ int stage_counts(scde_ctx*& ctx, const int* counts, int64_t ld, int ngenes, int 
 std::vector<double> marginals(const double* prior_x, int G);
 void seeding(int n_cores, long long gene_offset, long long N_total, int ngenes, std::vector<int>& seeds,
              std::vector<int>& wset);
+
+// ------------------------------------------------------------------ engine.hip, for engine_posterior.hip
+// the ordering tests' spin hook, before every event another stream or host thread waits on; and every
+// cross-stream wait: s waits for ev, then spins
+hipError_t handoff_spin(scde_ctx* cx, hipStream_t s);
+hipError_t handoff_wait(scde_ctx* cx, hipStream_t s, hipEvent_t ev);
+// the read-back thread: queue a 2-D read-back after the work queued so far on `after`; hold queued
+// read-backs back (on) or let them run (off)
+int dnl_push(scde_ctx* cx, hipStream_t after, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width,
+             size_t height);
+void dnl_hold(scde_ctx* cx, bool on);
+// every stream of the context that touches its workspace
+hipError_t ctx_streams_sync(scde_ctx* cx);
+
+// ------------------------------------------------------------------ engine_posterior.hip
+// ucl/uci of ns (1..4) cell subsets of the same device counts, on the context's stream
+int build_unique_sets(scde_ctx* cx, const PostSpec* const* s, scde_ctx::UniqueSet* const* u, int ns);
+// One posterior.  rest (nullable): return once the tables are queued, with the remaining work (modes,
+// draws, bootstrap, outputs) in *rest, to be run later on the same stream.  *rest refers to s and u:
+// the caller keeps both alive and unchanged until it has run.
 int run_posterior(scde_ctx* cx, const PostSpec& s, scde_ctx::UniqueSet& u, std::function<int()>* rest = nullptr);
 
 }  // namespace host

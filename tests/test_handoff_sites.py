@@ -4,8 +4,8 @@ tests/test_gpu_ordering.py makes a missing wait fail deterministically by queuei
 a stream after each of its cross-stream waits (so what it produces next starts late) and before
 each event another stream or host thread waits on (the test hook "handoff_spin",
 include/scde_hip.h).  That only covers the handoffs that call the hook, so this check reads
-the library's host code -- engine.hip (the pipeline, which holds every handoff today), the
-feature files api_*.hip and the header they share: each `hipEventRecord` is either one of the
+the library's host code -- engine.hip (the pipeline) and engine_posterior.hip (one posterior), which
+hold every handoff today, the feature files api_*.hip and the header they share: each `hipEventRecord` is either one of the
 profiling marks (timing events of one stream, never waited on by another) or is immediately
 preceded by a `handoff_spin(...)` on the same stream, and every `hipStreamWaitEvent` sits inside
 `handoff_wait`, which spins after the wait.  A new handoff added without the hook, in any of
@@ -17,8 +17,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "scde_amd", "csrc")
 ENGINE = os.path.join(CSRC, "engine.hip")
-HOST_FILES = ["engine.hip", "engine_internal.h"] + sorted(f for f in os.listdir(CSRC)
-                                                          if re.fullmatch(r"api_\w+\.hip", f))
+HOST_FILES = ["engine_internal.h"] + sorted(f for f in os.listdir(CSRC)
+                                            if re.fullmatch(r"engine\w*\.hip|api_\w+\.hip", f))
 
 
 def _sources():
@@ -52,7 +52,7 @@ def test_every_cross_stream_event_is_preceded_by_the_spin_hook():
 
 def test_every_cross_stream_wait_goes_through_handoff_wait():
     src = open(ENGINE).read()
-    m = re.search(r"static hipError_t handoff_wait\([^)]*\)\s*\{(.*?)\n\}", src, re.S)
+    m = re.search(r"\n(?:static )?hipError_t (?:scde::host::)?handoff_wait\([^)]*\)\s*\{(.*?)\n\}", src, re.S)
     assert m, "handoff_wait helper missing"
     body = m.group(1)
     assert "hipStreamWaitEvent" in body and "handoff_spin" in body
