@@ -1111,6 +1111,81 @@ int scde_nb2_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, 
                       const double* fail_prior, double background_rate, int max_iter, int lds_genes, double* models,
                       int* iterations, double* llh, int* status, int* clusters, double* post);
 
+/* ---------------------------------------------------------------- scde.error.models, the mixture cross-fit of pairs
+ * threshold.segmentation = FALSE: one three-component EM per pair of cells (calculate.crossfit.models'
+ * flexmix call, R/functions.R:2993-3028; csrc/crossfit_fit.hip; the contract, step by step and with
+ * what could not be checked against flexmix, is DESIGN.md section 4.19).  pairs holds the first
+ * cells pairs[0 .. npairs) and the second cells pairs[npairs .. 2 npairs) (host, two different cells
+ * each).  Per pair (i, j), c1 = counts[, i], c2 = counts[, j], thr = min.count.threshold:
+ *   rows         the genes with c1 + c2 > 0, in gene order; none: status 1
+ *   start        the posterior (c1 <= thr, c1 > thr and c2 > thr, c2 <= thr) as 0 / 1, divided by its
+ *                sum: (1/2, 0, 1/2) where both counts are <= thr
+ * then up to max_iter rounds of
+ *   shares       the mean over the rows of each component's posterior, as the round finds them; one
+ *                below min_prior ends the pair with status 6 (component lost)
+ *   concomitant  x = (log(c1 + 1) + log(c2 + 1)) / 2, pi = softmax(0, a2 + b2 x, a3 + b3 x); (a2, b2,
+ *                a3, b3) maximising sum_i sum_k p_ik log pi_ik by Newton from 0 with a 4 x 4 unpivoted
+ *                Cholesky, scde_knn_fit_*'s step halving and stopping rule; status 3 when a pivot is
+ *                not positive, a halving runs out or 50 steps do not meet the rule (separable data)
+ *   drivers      A: y = c1 on l = log(c2 + 1); B: y = c2 on l = log(c1 + 1); each scde_nb2_fit_*'s "NB
+ *                component" with w = p2 (divided by 1e6 where y <= 1), theta clamped to [0, 1e3], the
+ *                negative-slope rule, no underfit refit; status 2, 3 or 5 as there
+ *   E-step       a1 = log pi1 + dpois(c1, zero_lambda), a2 = log pi2 + dnbinom(c1; theta_A, mu_A) +
+ *                dnbinom(c2; theta_B, mu_B), a3 = log pi3 + dpois(c2, zero_lambda), all logs, mu =
+ *                max(exp(c0 + c1 l), 2^-52); posteriors softmax(a), llh = sum of the log-sum-exps
+ *                (not finite: status 3)
+ * until |llh - llh_old| / (|llh| + 0.1) < 1e-6.  Outputs (host; each may be NULL and is then not
+ * copied back): status, iterations (int32) and llh of npairs; params npairs x 10 column-major (a2,
+ * b2, a3, b3, then c0, c1, theta of A and of B; NaN for a failed pair, as llh); clusters int8,
+ * npairs blocks of ngenes: 1 / 2 / 3 the arg-max of the final posterior (the lowest index on a
+ * tie), 0 outside the pair's rows and throughout a failed pair; posterior, npairs blocks of 2 x
+ * ngenes: the final posterior of component 1, then of component 3, NaN where clusters is 0.
+ * clusters and posterior stay resident in the context for scde_crossfit_reduce_*.  One launch, one
+ * workgroup per pair; a pair with at most lds_rows rows (0: 2048; at most 2383) keeps its vectors
+ * in LDS, a larger one in HBM, with the same bits; every sum in an order fixed by the pair's row
+ * count and its rows of weight 0, no floating-point atomics; results are bit-repeatable, the same
+ * whichever pairs share the call, and the two entries agree bit for bit.  thr >= 0, 0 <= min_prior
+ * < 1, zero_lambda > 0, max_iter >= 1, at most 8192 cells.  ctx may be NULL. */
+int scde_crossfit_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const int* pairs,
+                          int npairs, int thr, double min_prior, double zero_lambda, int max_iter, int lds_rows,
+                          int* status, int* iterations, double* llh, double* params, int8_t* clusters,
+                          double* posterior);
+int scde_crossfit_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const int* pairs,
+                           int npairs, int thr, double min_prior, double zero_lambda, int max_iter, int lds_rows,
+                           int* status, int* iterations, double* llh, double* params, int8_t* clusters,
+                           double* posterior);
+
+/* ---------------------------------------------------------------- scde.error.models, from pair results to the fit's inputs
+ * scde_crossfit_inputs_* for any pairs' clusters and posteriors (R/functions.R:3147-3155, 3253-3303;
+ * csrc/error_models.hip).  pairs, status, clusters and posterior as
+ * scde_crossfit_fit_* takes and writes them (clusters holds codes 0 to 3); status, clusters and
+ * posterior all NULL: what the last scde_crossfit_fit_* call on this context left resident, which
+ * must have been given the same pairs and ngenes.  A pair's cells belong to one group and no pair
+ * is listed twice; pairs with a status other than 0 take no part; a cell that has pairs, all of
+ * them failed, is an error.  For gene g and cell c of a group of n cells:
+ *   vil[g, c]         c has a status-0 pair, and in every such pair g has cluster 2 or 3 where c is the
+ *                     pair's first cell, 1 or 2 where it is the second (never 0)
+ *   nabove[g, c]      the number of cells j != c of the group with vil[g, j]
+ *   valid, fpm        as scde_crossfit_inputs_*
+ *   fail_prior[g, c]  exp(mean(log q)) over c's status-0 pairs in which g is a row (q is not NaN), q
+ *                     the posterior of component 1 where c is the first cell and of component 3 where
+ *                     it is the second, the logs summed in the pairs' order; 1 - 1e-10 when there is
+ *                     no such pair; NaN when not valid
+ * (a row may carry cluster 0 with a posterior: the threshold rule's code for two low counts)
+ * vil (uint8), fpm, fail_prior (double) and nabove (int32) are host ngenes x ncells column-major;
+ * each may be NULL.  With ls NULL only vil is computed (the library sizes R derives from it are
+ * the host's work) and fpm, fail_prior and nabove must be NULL; with ls, fpm and fail_prior stay
+ * resident for scde_knn_fit_* / scde_nb2_fit_* as after scde_crossfit_inputs_*.  Bit-repeatable;
+ * the two entries agree bit for bit.  ctx may be NULL. */
+int scde_crossfit_reduce_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const int* groups, const double* ls, const int* pairs, int npairs, const int* status,
+                             const int8_t* clusters, const double* posterior, int min_nonfailed, uint8_t* vil,
+                             double* fpm, double* fail_prior, int* nabove);
+int scde_crossfit_reduce_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const int* groups, const double* ls, const int* pairs, int npairs, const int* status,
+                              const int8_t* clusters, const double* posterior, int min_nonfailed, uint8_t* vil,
+                              double* fpm, double* fail_prior, int* nabove);
+
 /* Free and total bytes of the context's device (hipMemGetInfo). */
 int scde_dev_mem_info(scde_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);
 

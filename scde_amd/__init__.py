@@ -17,7 +17,8 @@ from .cluster import (HClust, cutree, dist, hclust, hclust_batch, hclust_dist, l
 from .distance import (direct_dropout_distance, mode_relative_distance, reciprocal_distance,  # noqa: F401
                        weighted_correlation)
 from .embedding import TsneState, tsne_affinities, tsne_embedding, tsne_iterate  # noqa: F401
-from .error_models import crossfit_pairs, error_model_inputs, nb2_fit_models, scde_error_models  # noqa: F401
+from .error_models import (crossfit_models, crossfit_pairs, error_model_inputs, nb2_fit_models,  # noqa: F401
+                           scde_error_models, scde_fit_models_to_reference)
 from .knn import (estimate_library_sizes, knn_cell_data, knn_cell_similarity, knn_error_models,  # noqa: F401
                   knn_expected_magnitudes, knn_fit_models, knn_model_inputs, knn_neighbours, tmm_norm_factors)
 from .prep import clean_counts, clean_gos  # noqa: F401

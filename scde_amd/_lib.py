@@ -45,6 +45,7 @@ EXPORTS = [
     "scde_crossfit_inputs_dev", "scde_crossfit_inputs_host", "scde_nb2_fit_dev", "scde_nb2_fit_host",
     "scde_dist_host", "scde_dist_dev",
     "scde_rank_cols_dev", "scde_rank_cols_host", "scde_spearman_similarity_dev", "scde_spearman_similarity_host",
+    "scde_crossfit_fit_dev", "scde_crossfit_fit_host", "scde_crossfit_reduce_dev", "scde_crossfit_reduce_host",
 ]
 
 
@@ -186,6 +187,11 @@ def lib():
         L.scde_crossfit_inputs_dev.argtypes = L.scde_crossfit_inputs_host.argtypes = [P, P, i64, i, i, P, P, P, P, i,
                                                                                       i, P, P, P]
         L.scde_nb2_fit_dev.argtypes = L.scde_nb2_fit_host.argtypes = [P, P, i64, i, i, P, P, d, i, i, P, P, P, P, P, P]
+    if hasattr(L, "scde_crossfit_fit_dev"):  # (likewise: a build from before the mixture cross-fit)
+        L.scde_crossfit_fit_dev.argtypes = L.scde_crossfit_fit_host.argtypes = [P, P, i64, i, i, P, i, i, d, d, i, i, P,
+                                                                                P, P, P, P, P]
+        L.scde_crossfit_reduce_dev.argtypes = L.scde_crossfit_reduce_host.argtypes = [P, P, i64, i, i, P, P, P, i, P, P,
+                                                                                      P, i, P, P, P, P]
     if hasattr(L, "scde_dist_dev"):  # (likewise: a build from before stats::dist)
         L.scde_dist_host.argtypes = L.scde_dist_dev.argtypes = [P, P, i64, i, i, i, P]
     if hasattr(L, "scde_rank_cols_dev"):  # (likewise: a build from before Spearman)

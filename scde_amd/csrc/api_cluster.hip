@@ -1105,4 +1105,249 @@ int scde_crossfit_inputs_host(scde_ctx* ctx, const int* counts, int64_t ld, int 
   return scde_crossfit_inputs_dev(ctx, dev, ngenes, ngenes, ncells, groups, ls, part_off, part, thr, min_nonfailed,
                                   fpm, fail_prior, nabove);
 }
+
+// ------------------------------------------------------------------ the mixture cross-fit of pairs
+// crossfit_fit.hip; contract in scde_hip.h.  The pairs are checked before the GPU is touched: the
+// kernel indexes the counts with them.
+static int crossfit_fit_check(int ncells, const int* pairs, int npairs, int thr, double min_prior,
+                              double zero_lambda, int max_iter, int lds_rows) {
+  if (npairs < 0 || (npairs > 0 && !pairs)) return fail(SCDE_EARG, "crossfit_fit: null argument");
+  if (thr < 0) return fail(SCDE_EARG, "crossfit_fit: thr must not be negative");
+  if (!(min_prior >= 0.0) || !(min_prior < 1.0)) return fail(SCDE_EARG, "crossfit_fit: min_prior must lie in [0, 1)");
+  if (!(zero_lambda > 0.0) || std::isinf(zero_lambda))
+    return fail(SCDE_EARG, "crossfit_fit: zero_lambda must be a positive finite number");
+  if (max_iter < 1) return fail(SCDE_EARG, "crossfit_fit: max_iter must be at least 1");
+  if (lds_rows < 0 || lds_rows > crossfit_fit_lds_rows_max())
+    return fail(SCDE_EARG, "crossfit_fit: lds_rows must lie in [0, %d]", crossfit_fit_lds_rows_max());
+  for (int p = 0; p < npairs; ++p) {
+    const int a = pairs[p], b = pairs[(size_t)npairs + p];
+    if (a < 0 || a >= ncells || b < 0 || b >= ncells || a == b)
+      return fail(SCDE_EARG, "crossfit_fit: pair %d does not hold two different cells in [0, %d)", p, ncells);
+  }
+  return SCDE_OK;
+}
+
+int scde_crossfit_fit_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells, const int* pairs,
+                          int npairs, int thr, double min_prior, double zero_lambda, int max_iter, int lds_rows,
+                          int* status, int* iterations, double* llh, double* params, int8_t* clusters,
+                          double* posterior) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "crossfit_fit"));
+  RCHK(crossfit_fit_check(ncells, pairs, npairs, thr, min_prior, zero_lambda, max_iter, lds_rows));
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, P = npairs;
+  ctx->cf_n = ctx->cf_p = -1;
+  if (P == 0) {
+    ctx->cf_pairs_h.clear();
+    ctx->cf_status_h.clear();
+    ctx->cf_n = N;
+    ctx->cf_p = 0;
+    return SCDE_OK;
+  }
+  const int cap = lds_rows > 0 ? lds_rows : 2048;
+  int grid = 1;
+  HCHK(crossfit_fit_resident_groups(cap, &grid));
+  grid = std::min(grid, P);
+  const size_t np = std::max<size_t>(1, (size_t)N * P);
+  const size_t wsb = N > cap ? crossfit_fit_ws_bytes(N) * (size_t)grid : 0;
+  if ((wsb && ctx->cf_ws.ensure(wsb) != hipSuccess) || ctx->cf_cl.ensure(np) != hipSuccess ||
+      ctx->cf_post.ensure(sizeof(double) * 2 * np) != hipSuccess)
+    return fail_oom("crossfit_fit: out of memory: %d genes x %d pairs of results (%zu bytes) and a workspace of %zu "
+                    "bytes", N, P, 17 * np, wsb);
+  HCHK(ctx->cf_par.ensure(sizeof(double) * 11 * (size_t)P));
+  HCHK(ctx->cf_int.ensure(sizeof(int) * 4 * (size_t)P));
+  HCHK(hipMemcpyAsync(ctx->cf_int.p, pairs, sizeof(int) * 2 * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+  int* first = ctx->cf_int.as<int>();
+  int* st = first + 2 * (size_t)P;
+  int* its = st + P;
+  double* par = ctx->cf_par.as<double>();
+  double* lh = par + 10 * (size_t)P;
+  hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+  HCHK(launch_crossfit_fit(counts_dev, ld, N, P, first, first + P, thr, min_prior, zero_lambda, max_iter, cap,
+                           wsb ? ctx->cf_ws.as<char>() : nullptr, N, grid, st, its, lh, par,
+                           ctx->cf_cl.as<signed char>(), ctx->cf_post.as<double>(), ctx->stream));
+  ctx->mark_end(SLOT_OTHER, ev);
+  ctx->cf_status_h.assign((size_t)P, 0);
+  HCHK(hipMemcpyAsync(ctx->cf_status_h.data(), st, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+  if (iterations) HCHK(hipMemcpyAsync(iterations, its, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+  if (llh) HCHK(hipMemcpyAsync(llh, lh, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+  if (params) HCHK(hipMemcpyAsync(params, par, sizeof(double) * 10 * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+  if (clusters && N > 0)
+    HCHK(hipMemcpyAsync(clusters, ctx->cf_cl.p, (size_t)N * P, hipMemcpyDeviceToHost, ctx->stream));
+  if (posterior && N > 0)
+    HCHK(hipMemcpyAsync(posterior, ctx->cf_post.p, sizeof(double) * 2 * (size_t)N * P, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  RCHK(ctx->sync());
+  if (status) std::copy(ctx->cf_status_h.begin(), ctx->cf_status_h.end(), status);
+  ctx->cf_pairs_h.assign(pairs, pairs + 2 * (size_t)P);
+  ctx->cf_n = N;
+  ctx->cf_p = P;
+  return SCDE_OK;
+}
+
+int scde_crossfit_fit_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells, const int* pairs,
+                           int npairs, int thr, double min_prior, double zero_lambda, int max_iter, int lds_rows,
+                           int* status, int* iterations, double* llh, double* params, int8_t* clusters,
+                           double* posterior) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "crossfit_fit"));
+  RCHK(crossfit_fit_check(ncells, pairs, npairs, thr, min_prior, zero_lambda, max_iter, lds_rows));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_crossfit_fit_dev(ctx, dev, ngenes, ngenes, ncells, pairs, npairs, thr, min_prior, zero_lambda,
+                               max_iter, lds_rows, status, iterations, llh, params, clusters, posterior);
+}
+
+// ------------------------------------------------------------------ from pair results to the fit's inputs
+// error_models.hip's k_reduce_*; contract in scde_hip.h.
+struct ReduceLists {
+  CrossfitLists L;         // crossfit_check's, from the partner lists the pairs give
+  std::vector<int> plist;  // per cell, in the pairs' order: 2 * pair + side
+};
+
+static int crossfit_reduce_check(int ngenes, int ncells, const int* groups, const double* ls, const int* pairs,
+                                 int npairs, const int* status, const int8_t* clusters, int min_nonfailed,
+                                 ReduceLists* out) {
+  const int C = ncells, P = npairs;
+  if (P < 0 || (P > 0 && !pairs)) return fail(SCDE_EARG, "crossfit_reduce: null argument");
+  if (P > (1 << 30)) return fail(SCDE_EARG, "crossfit_reduce: too many pairs");
+  for (int p = 0; p < P; ++p) {
+    const int a = pairs[p], b = pairs[(size_t)P + p];
+    if (a < 0 || a >= C || b < 0 || b >= C || a == b)
+      return fail(SCDE_EARG, "crossfit_reduce: pair %d does not hold two different cells in [0, %d)", p, C);
+  }
+  std::vector<int> off((size_t)C + 1, 0), part(2 * (size_t)P);
+  for (int p = 0; p < P; ++p) {
+    ++off[(size_t)pairs[p] + 1];
+    ++off[(size_t)pairs[(size_t)P + p] + 1];
+  }
+  for (int c = 0; c < C; ++c) off[c + 1] += off[c];
+  std::vector<int> at(off.begin(), off.end() - 1);
+  out->plist.assign(2 * (size_t)P, 0);
+  for (int p = 0; p < P; ++p)
+    for (int side = 0; side < 2; ++side) {
+      const int c = pairs[(size_t)side * P + p], o = pairs[(size_t)(1 - side) * P + p];
+      part[at[c]] = o;
+      out->plist[at[c]++] = 2 * p + side;
+    }
+  std::vector<double> one;
+  if (!ls) one.assign((size_t)C, 1.0);
+  RCHK(crossfit_check(C, groups, ls ? ls : one.data(), off.data(), part.data(), 1, min_nonfailed, &out->L));
+  if (status) {
+    for (int c = 0; c < C; ++c) {
+      bool any = off[c + 1] == off[c];
+      for (int k = off[c]; k < off[c + 1] && !any; ++k) any = status[out->plist[k] >> 1] == 0;
+      if (!any) return fail(SCDE_EARG, "crossfit_reduce: every pair of cell %d failed", c);
+    }
+  }
+  if (clusters)
+    for (size_t i = 0; i < (size_t)ngenes * P; ++i)
+      if (clusters[i] < 0 || clusters[i] > 3)
+        return fail(SCDE_EARG, "crossfit_reduce: clusters must hold the codes 0 to 3");
+  return SCDE_OK;
+}
+
+int scde_crossfit_reduce_dev(scde_ctx* ctx, const int* counts_dev, int64_t ld, int ngenes, int ncells,
+                             const int* groups, const double* ls, const int* pairs, int npairs, const int* status,
+                             const int8_t* clusters, const double* posterior, int min_nonfailed, uint8_t* vil,
+                             double* fpm, double* fail_prior, int* nabove) {
+  FORK_GUARD();
+  RCHK(knn_check(counts_dev, ld, ngenes, ncells, "crossfit_reduce"));
+  const bool given = status || clusters || posterior;
+  if (given && npairs > 0 && !(status && clusters && posterior))
+    return fail(SCDE_EARG, "crossfit_reduce: status, clusters and posterior come together, or all NULL");
+  if (!ls && (fpm || fail_prior || nabove))
+    return fail(SCDE_EARG, "crossfit_reduce: without library sizes only vil is computed");
+  RCHK(use_ctx(ctx));
+  const int N = ngenes, C = ncells, P = npairs;
+  if (!given) {
+    if (ctx->cf_n != N || ctx->cf_p != P || !std::equal(ctx->cf_pairs_h.begin(), ctx->cf_pairs_h.end(), pairs))
+      return fail(SCDE_EARG, "crossfit_reduce: no resident fit of these %d pairs over %d genes (the last had %d "
+                             "pairs over %d genes)", P, N, ctx->cf_p, ctx->cf_n);
+    status = ctx->cf_status_h.data();
+  }
+  ReduceLists R;
+  RCHK(crossfit_reduce_check(N, C, groups, ls, pairs, P, status, given ? clusters : nullptr, min_nonfailed, &R));
+  const int G = R.L.ngroups;
+  ctx->ci_n = ctx->ci_c = -1;
+  const size_t nc = std::max<size_t>(1, (size_t)N * C), np = std::max<size_t>(1, (size_t)N * P);
+  if (ctx->kf_fpm.ensure(sizeof(double) * nc) != hipSuccess || ctx->kf_fp.ensure(sizeof(double) * nc) != hipSuccess ||
+      ctx->ci_nab.ensure(sizeof(int) * nc) != hipSuccess || ctx->cf_vil.ensure(nc) != hipSuccess ||
+      (given && (ctx->cf_cl.ensure(np) != hipSuccess || ctx->cf_post.ensure(sizeof(double) * 2 * np) != hipSuccess)))
+    return fail_oom("crossfit_reduce: out of memory: %d x %d results and %d x %d pair results need %zu bytes of "
+                    "device memory", N, C, N, P, 21 * nc + 17 * np);
+  if (given) {
+    ctx->cf_n = ctx->cf_p = -1;  // (the staging buffers are the resident pair results' home)
+    if (N > 0 && P > 0) {
+      HCHK(hipMemcpyAsync(ctx->cf_cl.p, clusters, (size_t)N * P, hipMemcpyHostToDevice, ctx->stream));
+      HCHK(hipMemcpyAsync(ctx->cf_post.p, posterior, sizeof(double) * 2 * (size_t)N * P, hipMemcpyHostToDevice,
+                          ctx->stream));
+    }
+  }
+  // the group lists and the partner offsets (crossfit_check's, its partner list replaced by the
+  // pair entries), the pairs' status, then the cells' valid-gene counters
+  std::vector<int>& v = R.L.ints;
+  const size_t head = (size_t)(G + 1) + C + C + (C + 1);
+  std::copy(R.plist.begin(), R.plist.end(), v.begin() + head);
+  const size_t so = v.size();
+  v.insert(v.end(), status, status + P);
+  const size_t li = v.size();
+  v.resize(li + (size_t)C, 0);
+  RCHK(upload(ctx, ctx->cf_red, v.data(), sizeof(int) * v.size()));
+  if (ls) RCHK(upload(ctx, ctx->ci_ls, ls, sizeof(double) * (size_t)C));
+  const int* goff = ctx->cf_red.as<int>();
+  const int* members = goff + G + 1;
+  const int* need = members + C;
+  const int* poff = need + C;
+  const int* pl = poff + C + 1;
+  const int* pst = ctx->cf_red.as<int>() + so;
+  int* nvalid = ctx->cf_red.as<int>() + li;
+  std::vector<int> nv((size_t)C, 0);
+  if (N > 0) {
+    hipEvent_t ev = ctx->mark_begin(SLOT_OTHER);
+    if (ls)
+      HCHK(launch_crossfit_reduce(counts_dev, ld, N, C, G, goff, members, need, poff, pl, pst,
+                                  ctx->cf_cl.as<signed char>(), ctx->cf_post.as<double>(), ctx->ci_ls.as<double>(),
+                                  ctx->cf_vil.as<unsigned char>(), ctx->kf_fpm.as<double>(), ctx->kf_fp.as<double>(),
+                                  ctx->ci_nab.as<int>(), nvalid, ctx->stream));
+    else
+      HCHK(launch_crossfit_vil(N, C, poff, pl, pst, ctx->cf_cl.as<signed char>(), ctx->cf_post.as<double>(),
+                               ctx->cf_vil.as<unsigned char>(), ctx->kf_fp.as<double>(), ctx->stream));
+    ctx->mark_end(SLOT_OTHER, ev);
+    HCHK(hipMemcpyAsync(nv.data(), nvalid, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t db = sizeof(double) * (size_t)N * C;
+    if (vil) HCHK(hipMemcpyAsync(vil, ctx->cf_vil.p, (size_t)N * C, hipMemcpyDeviceToHost, ctx->stream));
+    if (fpm) HCHK(hipMemcpyAsync(fpm, ctx->kf_fpm.p, db, hipMemcpyDeviceToHost, ctx->stream));
+    if (fail_prior) HCHK(hipMemcpyAsync(fail_prior, ctx->kf_fp.p, db, hipMemcpyDeviceToHost, ctx->stream));
+    if (nabove)
+      HCHK(hipMemcpyAsync(nabove, ctx->ci_nab.p, sizeof(int) * (size_t)N * C, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  RCHK(ctx->sync());
+  if (given) {
+    ctx->cf_pairs_h.assign(pairs, pairs + 2 * (size_t)P);
+    ctx->cf_status_h.assign(status, status + P);
+    ctx->cf_n = N;
+    ctx->cf_p = P;
+  }
+  if (ls) {
+    long long nmax = 0;
+    for (int c = 0; c < C; ++c) nmax = std::max<long long>(nmax, nv[c]);
+    ctx->ci_nmax = nmax;
+    ctx->ci_n = N;
+    ctx->ci_c = C;
+  }
+  return SCDE_OK;
+}
+
+int scde_crossfit_reduce_host(scde_ctx* ctx, const int* counts, int64_t ld, int ngenes, int ncells,
+                              const int* groups, const double* ls, const int* pairs, int npairs, const int* status,
+                              const int8_t* clusters, const double* posterior, int min_nonfailed, uint8_t* vil,
+                              double* fpm, double* fail_prior, int* nabove) {
+  FORK_GUARD();
+  RCHK(knn_check(counts, ld, ngenes, ncells, "crossfit_reduce"));
+  const int* dev = nullptr;
+  RCHK(stage_counts(ctx, counts, ld, ngenes, ncells, &dev));
+  return scde_crossfit_reduce_dev(ctx, dev, ngenes, ngenes, ncells, groups, ls, pairs, npairs, status, clusters,
+                                  posterior, min_nonfailed, vil, fpm, fail_prior, nabove);
+}
 }  // extern "C"

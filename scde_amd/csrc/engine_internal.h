@@ -270,6 +270,13 @@ struct scde_ctx {
   Buf ci_int, ci_ls, ci_nab;
   int ci_n = -1, ci_c = -1;
   long long ci_nmax = 0;
+  // the mixture cross-fit of pairs: the pairs' cells, status and iterations, the parameters and
+  // llh, the workspace; clusters (int8, cf_p blocks of cf_n genes) and the posteriors stay
+  // resident for scde_crossfit_reduce_* with the host's copy of the pairs and their status
+  // (cf_n = -1: nothing resident); the reduction's pair status, lists and vil
+  Buf cf_int, cf_par, cf_ws, cf_cl, cf_post, cf_red, cf_vil;
+  int cf_n = -1, cf_p = -1;
+  std::vector<int> cf_pairs_h, cf_status_h;
   // host-count entry points: the call's counts staged here (grow-only, reused across calls)
   Buf counts_in;
   // fixed-point bootstrap: byte multiplicities, flags/counters

@@ -621,6 +621,35 @@ hipError_t launch_nb2_fit(const int* counts, long long ld, int N, int C, const d
                           long long ws_cap, int grid, double* models, int* iters, double* llh, int* status,
                           int* clusters, double* post, hipStream_t s);
 
+// ---- the mixture cross-fit of cell pairs (crossfit_fit.hip; contract in include/scde_hip.h).
+// first, second: the P pairs' cells.  status (P) is always written; iters, llh (P), params (P x 10
+// column-major), clusters (P blocks of N int8) and post (P blocks of 2 x N: component 1, then
+// component 3) may each be null.  A pair with at most lds_rows rows keeps its vectors in LDS, a
+// larger one in its workgroup's slice of ws (crossfit_fit_ws_bytes(ws_cap) bytes per workgroup,
+// ws_cap at least the largest pair's rows; ws may be null when N <= lds_rows).
+int crossfit_fit_lds_rows_max();
+size_t crossfit_fit_lds_bytes(int lds_rows);
+size_t crossfit_fit_ws_bytes(long long ws_cap);
+hipError_t crossfit_fit_resident_groups(int lds_rows, int* groups);
+hipError_t launch_crossfit_fit(const int* counts, long long ld, int N, int P, const int* first, const int* second,
+                               int thr, double min_prior, double zero_lambda, int max_iter, int lds_rows, char* ws,
+                               long long ws_cap, int grid, int* status, int* iters, double* llh, double* params,
+                               signed char* clusters, double* post, hipStream_t s);
+
+// ---- from pair results to the per-cell fit's inputs (error_models.hip; contract in
+// include/scde_hip.h).  Lists as launch_crossfit_inputs'; the partner list is replaced by plist:
+// per cell, poff cuts its entries 2 * pair + side (side 1: the cell is the pair's second), in the
+// pairs' order.  pstatus (P), clusters and post as launch_crossfit_fit writes them.  vil: N x C
+// uint8.  launch_crossfit_vil is the first step alone (vil; fplog: N x C, the fail prior before vi).
+hipError_t launch_crossfit_vil(int N, int C, const int* poff, const int* plist, const int* pstatus,
+                               const signed char* clusters, const double* post, unsigned char* vil, double* fplog,
+                               hipStream_t s);
+hipError_t launch_crossfit_reduce(const int* counts, long long ld, int N, int C, int ngroups, const int* goff,
+                                  const int* members, const int* need, const int* poff, const int* plist,
+                                  const int* pstatus, const signed char* clusters, const double* post,
+                                  const double* ls, unsigned char* vil, double* fpm, double* fp, int* nabove,
+                                  int* nvalid, hipStream_t s);
+
 // ---- pagoda.top.aspects' matrix step (top_aspects.hip; contract in include/scde_hip.h).  x, w,
 // xv, xvw: m x C row-major (an aspect contiguous); num: m values.  Row r of xv is x's row centred
 // times num[r] / sqrt(its variance, denominator C - 1), row r of xvw is w's row over its sum

@@ -128,8 +128,16 @@ def _thr(thr):
     return int(thr)
 
 
-def library_size_genes(counts, min_size_entries=2000, thr=1):
-    """The genes (0-based, in R's order) estimate.library.sizes takes."""
+def _vil_arg(vil, shape):
+    vil = np.asarray(vil)
+    if vil.shape != shape:
+        raise ValueError("vil must be a genes x cells matrix, as the counts")
+    return vil != 0
+
+
+def library_size_genes(counts, min_size_entries=2000, thr=1, vil=None):
+    """The genes (0-based, in R's order) estimate.library.sizes takes.  ``vil`` (genes x cells,
+    non-zero: the observation is not a likely drop-out) replaces ``counts >= thr``."""
     counts = _host_counts(counts)
     N, C = counts.shape
     mse = int(min_size_entries)
@@ -139,19 +147,20 @@ def library_size_genes(counts, min_size_entries=2000, thr=1):
         raise ValueError(f"The number of valid genes ({N}) is lower then the specified min.size.entries ({mse}). "
                          "Please either increase min.size.entries or lower min.nonfailed parameter to increase the "
                          "number of valid genes")
-    nv = (counts >= _thr(thr)).sum(axis=1)
+    nv = ((counts >= _thr(thr)) if vil is None else _vil_arg(vil, counts.shape)).sum(axis=1)
     order = np.argsort(-nv, kind="stable")
     if nv[order[mse - 1]] < C:
         return order[:mse]
     return order[nv[order] == C]
 
 
-def estimate_library_sizes(counts, min_size_entries=2000, thr=1, norm_factors=None):
+def estimate_library_sizes(counts, min_size_entries=2000, thr=1, norm_factors=None, vil=None):
     """``estimate.library.sizes(counts, vil = counts >= thr)``: library sizes in millions of reads
     over the genes detected in the most cells, times the TMM factors (or ``norm_factors``), each
-    scaled to a geometric mean of 1."""
+    scaled to a geometric mean of 1.  ``vil``: the caller's matrix in the place of ``counts >= thr``
+    (the one the cross-fit gives: ``error_model_inputs(crossfit=)``)."""
     counts = _host_counts(counts)
-    sub = counts[library_size_genes(counts, min_size_entries, thr)].astype(np.float64)
+    sub = counts[library_size_genes(counts, min_size_entries, thr, vil)].astype(np.float64)
     if norm_factors is None:
         f = tmm_norm_factors(sub)
     else:
